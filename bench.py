@@ -26,8 +26,17 @@ bench therefore loads the library before its first GPU call, as a program linked
 against libmpi does before main().  `value` is that default; `sync_variants`
 shows what the headline loop gives without it and without kernarg-cache hits.
 
-Extra fields (rank 0):
-  value_conditions  what `value` was measured under (the headline).
+A plain run sets up, warms up, times the K steps and prints the line: `value`,
+`ms_per_step` (milliseconds per timed step), the per-rank rows, the
+call_distribution of those K calls and value_conditions (what `value` was
+measured under).  --dump-outputs DIR then writes what the last timed call left
+in its inoutbuf -- the array its caller receives -- to
+DIR/inoutbuf_rank<r>.npy (float32): the whole buffer up to DUMP_ELEMS elements
+over all ranks, else its first and last DUMP_EDGE elements and a seeded draw
+from between them (dump_indices).  The operands are seeded, so two runs with
+the same arguments write the same bits.
+
+Extra fields (rank 0), measured in runs of their own and only with --full:
   sync_variants the headline loop again with fresh kernel arguments on every
                 call (each misses the kernarg cache: BAR write + HDP flush), and
                 -- in a child process started before this one touches the GPU --
@@ -81,6 +90,8 @@ METRIC = "GiB/s device-resident MPI_Reduce_local (fp32 SUM, 256 MiB) at 1/2/4/8 
 NPAIRS = 4                     # operand pairs rotated through (>= 3)
 FRESH_OFFSETS = 256            # fresh-argument loop: 256 B steps x NPAIRS = 1024 distinct argument sets
 SLACK = FRESH_OFFSETS * 256    # bytes past each operand the fresh-argument offsets reach into
+DUMP_ELEMS = 1 << 22           # --dump-outputs: elements written over all ranks (16 MiB of float32)
+DUMP_EDGE = 4096               # of which the buffer's first and last DUMP_EDGE elements, always
 
 
 def parse():
@@ -92,11 +103,19 @@ def parse():
     ap.add_argument("--warmup", type=int, default=50,
                     help="untimed calls first: the GPU clocks and the kernarg cache settle (profiles/archive/r02/warmup_ab.log)")
     ap.add_argument("--mib", type=int, default=256, help="MiB per operand (metric: 256)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed MPI_Reduce_local loop")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: sync_variants, roofline, configs 2-5, stream_api, "
+                         "pcie_inclusive, host_resident, collectives (N > 1), cpu_baseline.  Without it the run "
+                         "sets up, warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed call left in its inoutbuf to "
+                         "DIR/inoutbuf_rank<r>.npy (float32; a fixed seeded sample when the buffer is larger "
+                         "than DUMP_ELEMS elements)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the roofline / configs / host blocks")
     ap.add_argument("--cpu-iters", type=int, default=24, help="cpu_baseline calls per thread")
     ap.add_argument("--collectives", choices=["auto", "on", "off"], default="auto",
-                    help="configs 4-5 via bench_coll.py in isolated child processes (auto: when N > 1)")
+                    help="with --full: configs 4-5 via bench_coll.py in isolated child processes (auto: when N > 1)")
     ap.add_argument("--cpu-standin", action="store_true",
                     help="TEST ONLY: gloo + a numpy step instead of the GPU call, to exercise the rank "
                          "launch and the max-over-ranks timing on a machine without GPUs")
@@ -104,7 +123,10 @@ def parse():
     ap.add_argument("--only-config5", action="store_true",
                     help="only the config5_combine block (fp16 two-operand and CHAIN8 kernels), for rocprofv3 passes")
     ap.add_argument("--variant-child", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.collectives == "on" and not args.full:
+        ap.error("--collectives on needs --full")
+    return args
 
 
 def spawn_ranks(args) -> int | None:
@@ -154,6 +176,8 @@ def cpu_standin(args) -> None:
 
     own, calls = [], []
     dt = time_steps(step, args.steps, args.warmup, lambda: None, barrier, max_over_ranks, own, calls)
+    if args.dump_outputs:
+        dump_output(args.dump_outputs, rank, world, a.size, lambda idx: a if idx is None else a[idx])
     alg = 3 * a.nbytes
     cstats = call_stats(calls, alg)
     rows = gather_rows([float(rank), own[0], cstats["median_us"]], world, dist, "cpu")
@@ -165,25 +189,53 @@ def cpu_standin(args) -> None:
            "data": "cpu stand-in (test only, not a measurement)"}
     # the collectives block's row format (bench_coll.coll_row) over the
     # stand-in's per-rank times, as the GPU run reports configs 4 and 5
-    import bench_coll
-    per = [r[1] / args.steps for r in rows]
-    out["collectives"] = {"stand_in": True,
-                          "config4_allreduce_fp32_sum_256MiB": {"rccl": bench_coll.coll_row(per, world, alg, "allreduce")},
-                          "config5_reduce_scatter_block_fp16_sum_1GiB": {
-                              "rccl": bench_coll.coll_row(per, world, alg, "reduce_scatter")}}
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full:
+        import bench_coll
+        per = [r[1] / args.steps for r in rows]
+        out["collectives"] = {"stand_in": True,
+                              "config4_allreduce_fp32_sum_256MiB": {"rccl": bench_coll.coll_row(per, world, alg, "allreduce")},
+                              "config5_reduce_scatter_block_fp16_sum_1GiB": {
+                                  "rccl": bench_coll.coll_row(per, world, alg, "reduce_scatter")}}
+    cpu_base = args.full and not args.no_cpu_baseline
+    if rank == 0 and cpu_base:
         # the real baseline routine on a small sample
         try:
             out["cpu_baseline"] = cpu_baseline(args, 1 << 16, 3 * (1 << 18))
         except Exception as exc:        # noqa: BLE001
             out["cpu_baseline"] = {"error": repr(exc)}
         out["cpu_baseline"]["ranks_parked"] = world - 1
-    if not args.no_cpu_baseline:
+    if cpu_base:
         park_until_rank0(world > 1, world, rank, dist, "bench_cpu_baseline_done")
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_indices(count: int, world: int):
+    """The elements of a `count`-element output that --dump-outputs writes: None
+    (all of them) when they fit this rank's share of DUMP_ELEMS, else its first
+    and last DUMP_EDGE elements and a seeded draw from between them, in index
+    order -- the same elements in every run with the same arguments."""
+    import numpy as np
+    n = max(DUMP_ELEMS // max(1, world), 4 * DUMP_EDGE)
+    if count <= n:
+        return None
+    mid = np.random.default_rng(0xD0).integers(DUMP_EDGE, count - DUMP_EDGE, size=n - 2 * DUMP_EDGE, dtype=np.int64)
+    mid.sort()
+    return np.concatenate([np.arange(DUMP_EDGE, dtype=np.int64), mid,
+                           np.arange(count - DUMP_EDGE, count, dtype=np.int64)])
+
+
+def dump_output(dirname: str, rank: int, world: int, count: int, take) -> str:
+    """--dump-outputs: the last timed call's inoutbuf (`take(idx)` returns its
+    elements `idx`, all `count` of them for None, as a numpy array) to
+    DIR/inoutbuf_rank<r>.npy in float32."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, f"inoutbuf_rank{rank}.npy")
+    np.save(path, np.ascontiguousarray(take(dump_indices(count, world)), dtype=np.float32))
+    return path
 
 
 def time_steps(step, k: int, w: int, sync, barrier, max_over_ranks, own: list | None = None,
@@ -379,7 +431,7 @@ def park_until_rank0(use_pg: bool, world: int, rank: int, dist, key: str, timeou
 
 def sync_loops(m, lib, reduce_local, ptrs, count, k: int, w: int, sync, barrier, max_over_ranks,
                own: list | None = None, c_loop=None, calls: list | None = None, gap: list | None = None,
-               bracket: list | None = None):
+               bracket: list | None = None, headline_only: bool = False, after_headline=None):
     """The headline loop (NPAIRS pairs rotated: every call after the first
     NPAIRS repeats its kernel arguments, which the direct dispatch's kernarg
     cache then holds) and the same loop with fresh arguments on every call: the
@@ -415,12 +467,18 @@ def sync_loops(m, lib, reduce_local, ptrs, count, k: int, w: int, sync, barrier,
     dt_py = None
     if c_loop is not None:
         dt = time_loop(runner(call_args), k, w, sync, barrier, max_over_ranks, own, calls, gap, bracket)
+    else:
+        dt = time_steps(step, k, w, sync, barrier, max_over_ranks, own, calls)
+    if after_headline is not None:
+        after_headline()
+    if headline_only:
+        return dt, None, None, step, None
+    if c_loop is not None:
         kw0 = lib.MPIR_Hip_direct_kernarg_writes()
         dtf = time_loop(runner(fresh_args), k, w, sync, barrier, max_over_ranks, own)
         writes = (lib.MPIR_Hip_direct_kernarg_writes() - kw0) / (k + w)
         dt_py = time_steps(step, k, w, sync, barrier, max_over_ranks)
     else:
-        dt = time_steps(step, k, w, sync, barrier, max_over_ranks, own, calls)
         kw0 = lib.MPIR_Hip_direct_kernarg_writes()
         dtf = time_steps(fstep, k, w, sync, barrier, max_over_ranks, own)
         writes = (lib.MPIR_Hip_direct_kernarg_writes() - kw0) / (k + w)
@@ -1010,7 +1068,7 @@ def main():
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # ROCm's own ring placement, in a child, before this process starts the GPU
     ring_variant = launch_variant = None
-    if world == 1 and not args.no_extras and not args.no_variants:
+    if world == 1 and args.full and not args.no_extras and not args.no_variants:
         ring_variant = run_variant_child(args)
         # the headline loop with the process left where it was launched
         launch_variant = run_variant_child(args, {"BENCH_BIND": "none"})
@@ -1018,7 +1076,7 @@ def main():
     # process starts the GPU: one process per rank holds a GPU at any time
     # (a child beside a live rank would double the processes on each card)
     coll = None
-    if args.collectives == "on" or (args.collectives == "auto" and world > 1 and not args.no_extras):
+    if args.full and (args.collectives == "on" or (args.collectives == "auto" and world > 1 and not args.no_extras)):
         coll = run_collectives_child(rank, world, local, lambda: None)
     import mpich_pip_amd as m
     # the library first, as a program linked against libmpi loads it before
@@ -1117,9 +1175,20 @@ def main():
     own, calls, gap, bracket = [], [], [], []
     place_before = m.placement(dev)
     d_before = lib.MPIR_Hip_direct_dispatches()
+
+    def dump():
+        # the last timed call was step W + K - 1: its inoutbuf is that pair's
+        # second buffer (the SLACK past `count` is not part of the call)
+        if args.dump_outputs and args.steps > 0:
+            res = pairs[(args.warmup + args.steps - 1) % NPAIRS][1][:count]
+            dump_output(args.dump_outputs, rank, world, count,
+                        lambda idx: (res if idx is None else res[torch.from_numpy(idx).to(res.device)]).cpu().numpy())
+    # the headline loop; with --full the same loop with fresh arguments and
+    # stepped from Python after it (sync_variants)
     dt, dt_fresh, fresh_writes, step, dt_py = sync_loops(m, lib, reduce_local, ptrs, count, args.steps,
                                                          args.warmup, sync, barrier, max_over_ranks, own, c_loop,
-                                                         calls, gap, bracket)
+                                                         calls, gap, bracket, headline_only=not args.full,
+                                                         after_headline=dump)
     # timed call i is step W + i: operand pair (W + i) % NPAIRS
     cstats = call_stats(calls, alg_bytes, [(args.warmup + i) % NPAIRS for i in range(len(calls))])
     if calls:
@@ -1136,13 +1205,14 @@ def main():
                 cstats["timed_region_loop_entry_us"] = round(bracket[0][2] * 1e6, 2)
                 cstats["timed_region_loop_exit_us"] = round(bracket[0][3] * 1e6, 2)
             cstats["opening_sync_us"] = round(bracket[0][4] * 1e6, 2)      # before t0, outside the region
-    direct_share = (lib.MPIR_Hip_direct_dispatches() - d_before) / ((3 if c_loop else 2) * (args.steps + args.warmup))
+    loops = (3 if c_loop else 2) if args.full else 1          # headline (+ fresh arguments, Python-stepped)
+    direct_share = (lib.MPIR_Hip_direct_dispatches() - d_before) / (loops * (args.steps + args.warmup))
     value = alg_bytes * args.steps * world / dt / GIB
     # each rank's own figures beside the max-over-ranks `value`: a lagging GPU,
     # or a rank whose calls left the direct path, shows here
     # where the timed loop's thread ran, relative to the GPU
     place = placement_record(m, dev)
-    rows = gather_rows([float(rank), float(dev), own[0], own[1], float(lib.MPIR_Hip_direct_state(dev)),
+    rows = gather_rows([float(rank), float(dev), own[0], own[1] if args.full else 0.0, float(lib.MPIR_Hip_direct_state(dev)),
                         direct_share, cstats["median_us"], cstats["p10_us"], cstats["p90_us"],
                         cstats["slow_share"], float(place_before["cpu"]), float(place["cpu"]),
                         float(place["cpu_node"]), float(place["gpu_node"]), float(place["signal_node"]),
@@ -1220,9 +1290,14 @@ def main():
                                   if c_loop else "perf_counter after each step of the timed loop (rank 0)"),
     }
 
-    variants = {"fresh_args": dict(rate(dt_fresh), kernarg_writes_per_call=round(fresh_writes, 3),
-                                   note="same loop, every call's arguments new (pairs shifted by multiples of "
-                                        "256 B, 1024 distinct sets): kernarg BAR write + HDP flush per call")}
+    variants = {}
+    if args.full:
+        variants["fresh_args"] = dict(rate(dt_fresh), kernarg_writes_per_call=round(fresh_writes, 3),
+                                      note="same loop, every call's arguments new (pairs shifted by multiples of "
+                                           "256 B, 1024 distinct sets): kernarg BAR write + HDP flush per call")
+    else:
+        for r in out["per_rank"]:
+            del r["fresh_args_seconds"]         # the fresh-argument loop runs with --full
     if dt_py is not None:
         variants["python_loop"] = dict(rate(dt_py), note="the headline loop stepped from Python: one compiled-binding "
                                                          "call per step (mpi4py's way), timed after the C loops")
@@ -1245,13 +1320,14 @@ def main():
                 HSA_ALLOCATE_QUEUE_DEV_MEM_seen=launch_variant.get("HSA_ALLOCATE_QUEUE_DEV_MEM"))
         else:
             variants["launch_placement"] = launch_variant
-    out["sync_variants"] = variants
+    if args.full:
+        out["sync_variants"] = variants
 
     if share:
         out["data"] = "REHEARSAL (BENCH_TEST_SHARE_GPU): %d ranks on %d GPU(s), not a measurement" % (
             world, torch.cuda.device_count())
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # ---- roofline: the synchronous call's kernel, timed by the CP's dispatch
         # timestamps of the direct AQL path (what rocprofv3 reads); its
         # HIP-launched twin timed with HIP events on its stream as a second figure
@@ -1398,14 +1474,15 @@ def main():
     # the CPU baseline on rank 0 at every N, after the GPU work, the other
     # ranks parked on a blocking store read (no spinning core beside it)
     unbind()
-    if rank == 0 and not args.no_cpu_baseline:
+    cpu_base = args.full and not args.no_cpu_baseline
+    if rank == 0 and cpu_base:
         try:
             out["cpu_baseline"] = cpu_baseline(args, count, alg_bytes)
         except Exception as exc:        # noqa: BLE001  (the parked ranks must still be released)
             out["cpu_baseline"] = {"error": repr(exc)}
         if world > 1:
             out["cpu_baseline"]["ranks_parked"] = world - 1
-    if not args.no_cpu_baseline:
+    if cpu_base:
         park_until_rank0(use_pg, world, rank, dist, "bench_cpu_baseline_done")
     if rank == 0:
         print(json.dumps(out), flush=True)

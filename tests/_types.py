@@ -239,3 +239,17 @@ def gen(t: str, n: int, rng: np.random.Generator, op: str = "MPI_SUM", specials:
 
 def to_bytes(a: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+
+
+def load_kat(gold: str):
+    """The known-answer cases of tests/golden: the manifest's case list and
+    every case's arrays (c<k>_ranks, c<k>_sol), read from the archives the
+    manifest names (tests/golden/make_golden.py writes two)."""
+    import json
+    import os
+    man = json.load(open(os.path.join(gold, "kat_reference.json")))
+    data = {}
+    for name in sorted(man["sha256_npz"]):
+        with np.load(os.path.join(gold, name)) as z:
+            data.update({k: z[k] for k in z.files})
+    return man["cases"], data

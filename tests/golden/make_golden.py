@@ -4,7 +4,7 @@
 Two fixture families, both DATA (inputs + expected outputs), no reference
 source:
 
-1. kat_reference.npz / kat_reference.json -- the reference's own
+1. kat_reference.npz + kat_reference_2.npz / kat_reference.json -- the reference's own
    known-answer tests, evaluated for rank counts p in {2, 3, 8}:
      * test/mpi/coll/allred.c:160-300 closed forms (sum_test1 `sol = i*size`,
        prod_test1 `sol = i^size`, max_test1 `i+size-1`, min_test1 `i`,
@@ -325,25 +325,34 @@ def main():
             allred_cases(p, count)
         opfile_cases(p)
         opfile_long_double_cases(p)
-    arrays, manifest = {}, []
+    # two archives, the cases' first and second half: thousands of small
+    # members make one archive larger than the 1 MiB a committed file may take
+    names = ("kat_reference.npz", "kat_reference_2.npz")
+    half = (len(cases) + 1) // 2
+    parts, manifest = ({}, {}), []
     for k, c in enumerate(cases):
+        arrays = parts[k >= half]
         arrays[f"c{k}_ranks"] = c["ranks"]
         arrays[f"c{k}_sol"] = c["sol"]
         manifest.append({"key": f"c{k}", "id": c["id"], "op": c["op"], "op_handle": OPS[c["op"]],
                          "datatype": c["datatype"], "handle": c["handle"], "p": c["p"], "count": c["count"],
                          "elem_bytes": int(c["sol"].size // c["count"])})
-    npz = os.path.join(HERE, "kat_reference.npz")
-    np.savez_compressed(npz, **arrays)
-    digest = hashlib.sha256(open(npz, "rb").read()).hexdigest()
+    digests = {}
+    for name, arrays in zip(names, parts):
+        npz = os.path.join(HERE, name)
+        np.savez_compressed(npz, **arrays)
+        digests[name] = hashlib.sha256(open(npz, "rb").read()).hexdigest()
+        assert os.path.getsize(npz) < (1 << 20), name
     with open(os.path.join(HERE, "kat_reference.json"), "w") as f:
-        json.dump({"generator": "tests/golden/make_golden.py", "sha256_npz": digest,
+        json.dump({"generator": "tests/golden/make_golden.py", "sha256_npz": digests,
                    "source": "test/mpi/coll/allred.c, opsum.c, opmax.c, opmin.c, opprod.c, oplxor.c, opmaxloc.c, "
                              "opminloc.c closed forms",
                    "cases": manifest}, f, indent=0)
     with open(os.path.join(HERE, "probe_survey.json"), "w") as f:
         json.dump({"generator": "tests/golden/make_golden.py",
                    "note": "bit patterns; inout = a (the reference's a[i]), in = b", "cases": probes()}, f, indent=1)
-    print(f"{len(cases)} KAT cases, npz {os.path.getsize(npz)} bytes")
+    print(f"{len(cases)} KAT cases, npz " + " + ".join(str(os.path.getsize(os.path.join(HERE, n))) for n in names)
+          + " bytes")
 
 
 if __name__ == "__main__":

@@ -26,7 +26,7 @@ def test_bench_under_torchrun_with_rccl_group():
     env = dict(os.environ, BENCH_TEST_PG="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "1", "--steps", "5", "--warmup", "2", "--mib", "64", "--no-extras", "--no-variants",
+           "--gpus", "1", "--steps", "5", "--warmup", "2", "--mib", "64", "--full", "--no-extras", "--no-variants",
            "--no-cpu-baseline", "--collectives", "on"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]

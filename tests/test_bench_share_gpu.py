@@ -20,7 +20,7 @@ def test_bench_two_ranks_share_one_gpu():
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["BENCH_TEST_SHARE_GPU"] = "1"
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4",
-                        "--warmup", "2", "--mib", "64", "--no-extras"],
+                        "--warmup", "2", "--mib", "64", "--full", "--no-extras"],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=100)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

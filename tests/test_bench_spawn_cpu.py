@@ -33,6 +33,40 @@ def test_bench_single_rank_does_not_spawn():
     assert [r["rank"] for r in out["per_rank"]] == [0]
 
 
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without --full the line is the headline alone (no cpu_baseline, no
+    collectives); --dump-outputs writes the last step's result in float32, the
+    same bits from run to run.  The stand-in's step is a += 1 from ones."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        out = _run(["--gpus", "1", "--steps", "3", "--warmup", "2", "--cpu-standin", "--dump-outputs", str(tmp_path / d)])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        assert "cpu_baseline" not in out and "collectives" not in out
+        outs.append(np.load(tmp_path / d / "inoutbuf_rank0.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (1 << 16,)
+    assert np.array_equal(outs[0], np.full(1 << 16, 6.0, np.float32))        # 1 + (W + K) * 1
+    assert np.array_equal(outs[0].view(np.uint32), outs[1].view(np.uint32))
+
+
+def test_dump_indices_fixed_sample():
+    """A buffer past the dump's size is sampled: both edges whole, a seeded draw
+    between, in index order, within bounds, identical on every call; the whole
+    dump stays under 64 MB over all ranks."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_indices(bench.DUMP_ELEMS, 1) is None
+    n = 1 << 26
+    for world in (1, 8):
+        idx = bench.dump_indices(n, world)
+        assert idx.dtype == np.int64 and len(idx) * 4 * world <= 64 * 10 ** 6
+        assert idx.min() == 0 and idx.max() == n - 1 and np.all(np.diff(idx) >= 0)
+        e = bench.DUMP_EDGE
+        assert np.array_equal(idx[:e], np.arange(e)) and np.array_equal(idx[-e:], np.arange(n - e, n))
+        assert np.array_equal(idx, bench.dump_indices(n, world))
+
+
 def test_bench_eight_ranks_report_per_rank():
     """at N > 1 the line carries every rank's own timed loop
     beside the max-over-ranks value, so a lagging GPU (or a rank off the direct
@@ -40,7 +74,8 @@ def test_bench_eight_ranks_report_per_rank():
     carries (a) the collectives' per-rank times and xGMI fractions, (b) the CPU
     baseline from rank 0 with the other ranks parked, (c) the timed calls'
     median and p10 / p90.  8 gloo ranks on the CPU."""
-    out = _run(["--gpus", "8", "--steps", "5", "--warmup", "1", "--cpu-standin", "--cpu-iters", "1"], timeout=400)
+    out = _run(["--gpus", "8", "--steps", "5", "--warmup", "1", "--cpu-standin", "--full", "--cpu-iters", "1"],
+               timeout=400)
     assert out["n_gpus"] == 8
     pr = out["per_rank"]
     assert [r["rank"] for r in pr] == list(range(8))

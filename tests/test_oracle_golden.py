@@ -19,17 +19,19 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def load_kat():
-    man = json.load(open(os.path.join(GOLD, "kat_reference.json")))
-    data = np.load(os.path.join(GOLD, "kat_reference.npz"))
-    return man["cases"], data
+    return T.load_kat(GOLD)
 
 
 def test_golden_files_match_manifest():
     import hashlib
     man = json.load(open(os.path.join(GOLD, "kat_reference.json")))
-    digest = hashlib.sha256(open(os.path.join(GOLD, "kat_reference.npz"), "rb").read()).hexdigest()
-    assert digest == man["sha256_npz"]
+    assert len(man["sha256_npz"]) == 2
+    for name, want in man["sha256_npz"].items():
+        digest = hashlib.sha256(open(os.path.join(GOLD, name), "rb").read()).hexdigest()
+        assert digest == want, name
     assert len(man["cases"]) > 2000
+    cases, data = load_kat()
+    assert set(data) == {c["key"] + s for c in cases for s in ("_ranks", "_sol")}
 
 
 def test_oracle_folds_reference_kats(orc):

@@ -152,8 +152,7 @@ def test_relative_misalignment_tile_path(mpi, orc, cuda, op, t):
 def test_golden_kat_fold_on_gpu(mpi, cuda):
     """The reference's own known-answer tests, folded on the GPU, bit for bit."""
     torch = cuda
-    man = json.load(open(os.path.join(GOLD, "kat_reference.json")))["cases"]
-    data = np.load(os.path.join(GOLD, "kat_reference.npz"))
+    man, data = T.load_kat(GOLD)
     bad = []
     for c in man:
         ranks = data[c["key"] + "_ranks"]

@@ -9,12 +9,12 @@
 #   fold       tools/fold_trace (fused fold workgroup trace + candidate shapes)
 #   local      tools/local_ranks_ab.py (8 concurrent host-combine ranks)
 #   smoke      __graft_entry__.smoke()
-#   bench      python bench.py (defaults)
+#   bench      python bench.py --full (defaults)
 #   prof       tools/profile_r03.sh: kernel trace + stats at 256 / 64 MiB, FETCH_SIZE and WRITE_SIZE passes
 #   lds        tools/archive/lds_cap_cost (a fused fold beside a streaming kernel)
 #   hostlat    tools/host_small_latency gpu
-#   driver6    python bench.py --steps 20 --warmup 5 (the driver's shape), six fresh processes
-#   bench20    python bench.py --steps 20 --warmup 5, once (round 6: one bench pass per product change)
+#   driver6    python bench.py --full --steps 20 --warmup 5 (the driver's shape), six fresh processes
+#   bench20    python bench.py --full --steps 20 --warmup 5, once (round 6: one bench pass per product change)
 #   classifyt  tests/test_classify_kinds_gpu.py (pointer kinds, kept verdicts)
 #   bindt      tests/test_bind_gpu.py (the binding and signal-node knobs)
 #   place      tools/placement_ab.py (near / far / as-launched caller, alternated processes)
@@ -52,14 +52,14 @@ for step in "$@"; do
            cat $OUT/local_ranks_ab.log ;;
     smoke) timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; rc=$?
            tail -5 $OUT/smoke.log ;;
-    bench) timeout -k 10 400 python -u bench.py > $OUT/bench.log 2>&1; rc=$?; tail -c 3000 $OUT/bench.log ;;
+    bench) timeout -k 10 400 python -u bench.py --full > $OUT/bench.log 2>&1; rc=$?; tail -c 3000 $OUT/bench.log ;;
     prof) timeout -k 10 1100 bash tools/profile_r03.sh $TAG > $OUT/prof.log 2>&1; rc=$?; tail -3 $OUT/prof.log ;;
     lds) timeout -k 10 300 tools/archive/lds_cap_cost > $OUT/lds_cap_cost.log 2>&1; rc=$?; cat $OUT/lds_cap_cost.log ;;
     hostlat) timeout -k 10 200 tools/host_small_latency gpu > $OUT/host_small_latency.log 2>&1; rc=$?
              cat $OUT/host_small_latency.log ;;
     driver6) rc=0
              for i in 1 2 3 4 5 6; do
-                 timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 > $OUT/bench_ds_$i.log 2>&1 || { rc=$?; break; }
+                 timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 > $OUT/bench_ds_$i.log 2>&1 || { rc=$?; break; }
                  python - $OUT/bench_ds_$i.log <<'PY'
 import json, sys
 d = [json.loads(l) for l in open(sys.argv[1]) if l.startswith("{")][-1]
@@ -68,7 +68,7 @@ print(f"{sys.argv[1]}: value {d['value']} = {d['per_gpu']['frac_of_hbm_peak']}, 
       f"({d['roofline']['frac']}), call median {c['median_us']} p90 {c['p90_us']}, fixed {c['decomposition']['fixed_us']}")
 PY
              done ;;
-    bench20) timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > $OUT/bench20.log 2>&1; rc=$?
+    bench20) timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > $OUT/bench20.log 2>&1; rc=$?
              tail -c 3000 $OUT/bench20.log ;;
     classifyt) timeout -k 10 300 python -u -m pytest -x -v --timeout 120 --timeout-method thread \
                 tests/test_classify_kinds_gpu.py > $OUT/pytest_classify.log 2>&1; rc=$?; tail -4 $OUT/pytest_classify.log ;;
