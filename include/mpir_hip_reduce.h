@@ -81,6 +81,36 @@ int MPIR_Hip_reduce(const void *inbuf, void *inoutbuf, uint64_t count, int op, i
 int MPIR_Hip_combine(const void *const *inbufs, int n, void *outbuf, uint64_t count, int op, int elem,
                      int order, void *hip_stream, int sync);
 
+/* For tests and tools: the launch plan MPIR_Hip_reduce would take for device
+ * operands at these addresses, from the same planner the launch calls -- host
+ * arithmetic on the pointer values only (they are never dereferenced or
+ * classified; no GPU is needed).  out = {kind, groups, nhead, ntail, vbytes,
+ * keep}: the plan kind below, its grid in workgroups, the elements workgroup 0
+ * combines before / after the 16-byte vector region, that region's bytes, and
+ * the bytes of it stored sc1 (0: all nt; MPIR_Hip_set_keep_bytes).  The element
+ * kinds report nhead = ntail = vbytes = keep = 0.  MPIR_HIP_ENOKERNEL where
+ * (op, elem) has no planned kernel (REPLACE's byte copy included). */
+#define MPIR_HIP_PLAN_LEAN        0   /* tile kernel, no head / tail */
+#define MPIR_HIP_PLAN_FULL        1   /* tile kernel with head / tail elements */
+#define MPIR_HIP_PLAN_SHIFT       2   /* inbuf at another offset mod 16 than inoutbuf, >= 2 tiles */
+#define MPIR_HIP_PLAN_ELEMS       3   /* element kernel, naturally aligned */
+#define MPIR_HIP_PLAN_ELEMS_U     4   /* element kernel, unaligned elements */
+#define MPIR_HIP_PLAN_WIDE_TILE   5   /* 32-byte classes: LDS-transpose tile kernel */
+#define MPIR_HIP_PLAN_WIDE_ELEMS  6   /* 32-byte classes off 16 B alignment: element kernel */
+int MPIR_Hip_plan_info(const void *inbuf, const void *inoutbuf, uint64_t count, int op, int elem, uint64_t out[6]);
+
+/* For tests and tools: the same for MPIR_Hip_combine.  out = {path, passes,
+ * nhead, ntail}: the path below; the kernel launches (1, or 2-9 for a CHAIN of
+ * more than 8 operands with a fused fold); the head / tail elements of the
+ * fused vector kernel (0 on the other paths).  A multi-pass CHAIN reports
+ * fused-elements if any of its passes takes the element kernel. */
+#define MPIR_HIP_COMBINE_PATH_COPY           0   /* n == 1, or REPLACE: a device copy (none if in place) */
+#define MPIR_HIP_COMBINE_PATH_FUSED_VECTOR   1   /* k_combine_multi */
+#define MPIR_HIP_COMBINE_PATH_FUSED_ELEMENTS 2   /* k_combine_multi_elems: an operand off the output's alignment */
+#define MPIR_HIP_COMBINE_PATH_ANY            3   /* k_combine_any */
+int MPIR_Hip_combine_plan_info(const void *const *inbufs, int n, const void *outbuf, uint64_t count, int op, int elem,
+                               int order, uint64_t out[4]);
+
 /* Flags for the calling thread's later MPIR_Hip_combine calls; returns the
  * previous flags.  MPIR_HIP_COMBINE_UNCAPPED: the fused folds run without the
  * LDS reservation that caps a CU at one (P >= 5) or three (P = 3, 4) of their

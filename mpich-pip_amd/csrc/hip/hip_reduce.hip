@@ -1073,6 +1073,47 @@ int device_call(int dev, const void *inbuf, void *inoutbuf, uint64_t count, int 
     return rc;
 }
 
+// Which branch of MPIR_Hip_combine a fold of n operands takes, in its order
+// (MPIR_Hip_combine launches it, MPIR_Hip_combine_plan_info reports it)
+enum CombineRoute { ROUTE_COPY_FIRST, ROUTE_COPY_LAST, ROUTE_FUSED_TREE, ROUTE_FUSED_CHAIN, ROUTE_ANY, ROUTE_NONE };
+CombineRoute combine_route(int n, int op, int elem, int order) {
+    const bool fused = g_multi[op][elem][0][0] != nullptr;
+    if (n == 1) return ROUTE_COPY_FIRST;
+    // a fold of REPLACE in either order is the last operand
+    if (op == MPIR_HIP_OP_REPLACE) return ROUTE_COPY_LAST;
+    if (order == MPIR_HIP_ORDER_TREE && fused && n <= 8) return ROUTE_FUSED_TREE;
+    if (order == MPIR_HIP_ORDER_CHAIN && fused) return ROUTE_FUSED_CHAIN;
+    if (g_table[op][elem].any) return ROUTE_ANY;
+    return ROUTE_NONE;
+}
+
+// the argument checks MPIR_Hip_combine makes before it looks at a pointer
+bool combine_args_ok(int n, int op, int elem, int order) {
+    if (n < 1 || n > 64 || (order != MPIR_HIP_ORDER_TREE && order != MPIR_HIP_ORDER_CHAIN)) return false;
+    if (op <= 0 || op >= MPIR_HIP_NOPS || elem <= 0 || elem >= MPIR_HIP_NELEMS) return false;
+    return !(order == MPIR_HIP_ORDER_TREE && (n & (n - 1)));
+}
+
+// CHAIN beyond 8 operands: chunks of up to 8, each chunk's first operand the
+// running acc (the output after the first pass).  fn(ops, P) per pass, until it
+// returns false; returns the passes made.
+template <class F>
+int chain_passes(const void *const *inbufs, int n, const void *outbuf, F fn) {
+    const void *acc = inbufs[0];
+    int passes = 0;
+    for (int i = 1; i < n;) {
+        const int P = std::min(kMultiMaxP, n - i + 1);
+        const void *ops[kMultiMaxP];
+        ops[0] = acc;
+        for (int j = 1; j < P; ++j) ops[j] = inbufs[i + j - 1];
+        ++passes;
+        if (!fn(ops, P)) break;
+        i += P - 1;
+        acc = outbuf;
+    }
+    return passes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1155,9 +1196,7 @@ int MPIR_Hip_memcpy(void *dst, const void *src, size_t bytes) {
 int MPIR_Hip_combine(const void *const *inbufs, int n, void *outbuf, uint64_t count, int op, int elem,
                      int order, void *hip_stream, int sync) {
     ctx().err[0] = 0;
-    if (n < 1 || n > 64 || (order != MPIR_HIP_ORDER_TREE && order != MPIR_HIP_ORDER_CHAIN)) return MPIR_HIP_ENOKERNEL;
-    if (op <= 0 || op >= MPIR_HIP_NOPS || elem <= 0 || elem >= MPIR_HIP_NELEMS) return MPIR_HIP_ENOKERNEL;
-    if (order == MPIR_HIP_ORDER_TREE && (n & (n - 1))) return MPIR_HIP_ENOKERNEL;
+    if (!combine_args_ok(n, op, elem, order)) return MPIR_HIP_ENOKERNEL;
     const size_t esz = g_elem_size[elem];
     int dev = -1;
     if (classify(outbuf, &dev) != LOC_DEVICE) return MPIR_HIP_EBUFFER;
@@ -1173,41 +1212,117 @@ int MPIR_Hip_combine(const void *const *inbufs, int n, void *outbuf, uint64_t co
     if (!s) rc = get_stream(dev, S_MAIN, &s);
     hipError_t e = hipSuccess;
     if (rc == MPIR_HIP_OK && count > 0) {
-        const bool fused = g_multi[op][elem][0][0] != nullptr;
-        if (n == 1) {
+        switch (combine_route(n, op, elem, order)) {
+        case ROUTE_COPY_FIRST:
             if (outbuf != inbufs[0]) e = hipMemcpyAsync(outbuf, inbufs[0], count * esz, hipMemcpyDeviceToDevice, s);
-        } else if (op == MPIR_HIP_OP_REPLACE) {
-            // a fold of REPLACE in either order is the last operand
+            break;
+        case ROUTE_COPY_LAST:
             if (outbuf != inbufs[n - 1])
                 e = hipMemcpyAsync(outbuf, inbufs[n - 1], count * esz, hipMemcpyDeviceToDevice, s);
-        } else if (order == MPIR_HIP_ORDER_TREE && fused && n <= 8) {
+            break;
+        case ROUTE_FUSED_TREE:
             e = g_multi[op][elem][0][n - 2](inbufs, outbuf, count, s);
-        } else if (order == MPIR_HIP_ORDER_CHAIN && fused) {
-            // CHAIN: acc = y0; fold y1..y_{n-1} in order, one pass for n <= 8;
-            // beyond, chunks of up to 8 operands, each chunk's first operand the
-            // running acc
-            const void *acc = inbufs[0];
-            int i = 1;
-            while (e == hipSuccess && i < n) {
-                const int P = std::min(kMultiMaxP, n - i + 1);
-                const void *ops[kMultiMaxP];
-                ops[0] = acc;
-                for (int j = 1; j < P; ++j) ops[j] = inbufs[i + j - 1];
+            break;
+        case ROUTE_FUSED_CHAIN:
+            // CHAIN: acc = y0; fold y1..y_{n-1} in order, one pass for n <= 8
+            // (chain_passes beyond)
+            chain_passes(inbufs, n, outbuf, [&](const void *const *ops, int P) {
                 e = g_multi[op][elem][1][P - 2](ops, outbuf, count, s);
-                i += P - 1;
-                acc = outbuf;
-            }
-        } else if (g_table[op][elem].any) {
+                return e == hipSuccess;
+            });
+            break;
+        case ROUTE_ANY:
             // one pass, no temporaries (k_combine_any)
             e = g_table[op][elem].any(inbufs, n, order == MPIR_HIP_ORDER_TREE, outbuf, count, s);
-        } else {
+            break;
+        default:
             rc = MPIR_HIP_ENOKERNEL;
+            break;
         }
         if (e != hipSuccess) rc = set_err(e, "combine launch");
         if (rc == MPIR_HIP_OK && sync) rc = wait_stream(dev, s);
     }
     if (cur != dev) (void)hipSetDevice(cur);
     return rc;
+}
+
+int MPIR_Hip_plan_info(const void *inbuf, const void *inoutbuf, uint64_t count, int op, int elem, uint64_t out[6]) {
+    if (op <= 0 || op >= MPIR_HIP_NOPS || elem <= 0 || elem >= MPIR_HIP_NELEMS) return MPIR_HIP_ENOKERNEL;
+    const Entry &en = g_table[op][elem];
+    const plan_fn fn = en.plan ? en.plan : en.wide;
+    if (!en.fn || !fn) return MPIR_HIP_ENOKERNEL;
+    ReducePlan p;
+    fn(inbuf, const_cast<void *>(inoutbuf), count, &p);
+    uint64_t nhead = 0, ntail = 0, vbytes = 0, keep = 0;
+    switch (p.kind) {
+    case kPlanLean:
+    case kPlanWideTile: {
+        LeanArgs a;
+        memcpy(&a, p.args, sizeof a);
+        vbytes = a.vbytes;
+        keep = a.keep;
+        break;
+    }
+    case kPlanFull:
+    case kPlanShift: {
+        // TileArgs<T> has one layout for every T (pointers and sizes); it leads ShiftArgs<T>
+        TileArgs<char> a;
+        memcpy(&a, p.args, sizeof a);
+        nhead = a.nhead;
+        ntail = a.ntail;
+        vbytes = a.vbytes;
+        keep = a.keep;
+        break;
+    }
+    default:
+        break;
+    }
+    out[0] = (uint64_t)p.kind;
+    out[1] = p.groups;
+    out[2] = nhead;
+    out[3] = ntail;
+    out[4] = vbytes;
+    out[5] = keep;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_combine_plan_info(const void *const *inbufs, int n, const void *outbuf, uint64_t count, int op, int elem,
+                               int order, uint64_t out[4]) {
+    if (!combine_args_ok(n, op, elem, order)) return MPIR_HIP_ENOKERNEL;
+    uint64_t path = MPIR_HIP_COMBINE_PATH_COPY, passes = 1, nhead = 0, ntail = 0;
+    switch (combine_route(n, op, elem, order)) {
+    case ROUTE_COPY_FIRST:
+    case ROUTE_COPY_LAST:
+        break;
+    case ROUTE_FUSED_TREE:
+    case ROUTE_FUSED_CHAIN: {
+        const split_fn split = g_table[op][elem].split;
+        if (!split) return MPIR_HIP_ENOKERNEL;
+        path = MPIR_HIP_COMBINE_PATH_FUSED_VECTOR;
+        auto pass = [&](const void *const *ops, int P) {
+            CombineSplit c;
+            split(ops, P, outbuf, count, &c);
+            if (!c.vec_ok) path = MPIR_HIP_COMBINE_PATH_FUSED_ELEMENTS;
+            nhead = c.nhead;        // the same in every vector pass: out and count alone set them
+            ntail = c.ntail;
+            return true;
+        };
+        if (order == MPIR_HIP_ORDER_TREE) pass(inbufs, n);
+        else passes = (uint64_t)chain_passes(inbufs, n, outbuf, pass);
+        if (path == MPIR_HIP_COMBINE_PATH_FUSED_ELEMENTS) nhead = ntail = 0;
+        break;
+    }
+    case ROUTE_ANY:
+        path = MPIR_HIP_COMBINE_PATH_ANY;
+        break;
+    default:
+        return MPIR_HIP_ENOKERNEL;
+    }
+    out[0] = path;
+    out[1] = passes;
+    out[2] = nhead;
+    out[3] = ntail;
+    return MPIR_HIP_OK;
 }
 
 int MPIR_Hip_reduce(const void *inbuf, void *inoutbuf, uint64_t count, int op, int elem, void *hip_stream,

@@ -30,12 +30,16 @@ typedef hipError_t (*any_fn)(const void *const *, int, int, void *, uint64_t, hi
 typedef hipError_t (*multi_fn)(const void *const *, void *, uint64_t, hipStream_t);
 typedef void (*host_fn)(const void *, void *, uint64_t);
 typedef void (*plan_fn)(const void *, void *, uint64_t, ReducePlan *);
+typedef void (*split_fn)(const void *const *, int, const void *, uint64_t, CombineSplit *);
 
 // plan: plan_reduce<T> (reduce_kernels.hpp) for the classes whose launcher is
 // launch_reduce -- the kernel, grid and argument bytes the direct AQL dispatch
 // launches from its code object; null for the 32-byte classes (LDS transpose)
-// and REPLACE (a byte copy), which take the HIP launch
-struct Entry { launch_fn fn; any_fn any; host_fn host; plan_fn plan; };
+// and REPLACE (a byte copy), which take the HIP launch.
+// wide: plan_reduce_wide<T, EPL> for the 32-byte classes (what launch_reduce_wide
+// launches); split: combine_split<T> for the pairs with fused folds (what
+// launch_combine_pu launches).  Both are read by the plan introspection only.
+struct Entry { launch_fn fn; any_fn any; host_fn host; plan_fn plan; plan_fn wide; split_fn split; };
 
 // float / double SUM and PROD on the host: the SSE instruction itself.  The
 // reference's loop `a[i] = a[i] + b[i]` (opsum.c:21-76, gcc -O2) is an
@@ -118,11 +122,13 @@ void reg(int op, int elem) {
 template <class Op, class T, int EPL = 2>
 void reg_wide(int op, int elem) {
     g_table[op][elem].fn = &launch_reduce_wide<Op, T, EPL>;
+    g_table[op][elem].wide = &plan_reduce_wide<T, EPL>;
     g_table[op][elem].host = &host_loop<Op, T>;
     g_table[op][elem].any = &launch_combine_any<Op, T>;
 }
 template <class Op, class T>
 void reg_multi(int op, int elem) {
+    g_table[op][elem].split = &combine_split<T>;
     g_multi[op][elem][0][2 - 2] = &launch_combine_p<Op, T, 2, true>;
     g_multi[op][elem][0][4 - 2] = &launch_combine_p<Op, T, 4, true>;
     g_multi[op][elem][0][8 - 2] = &launch_combine_p<Op, T, 8, true>;

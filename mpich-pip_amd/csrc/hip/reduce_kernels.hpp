@@ -372,7 +372,10 @@ enum : int {
     kPlanShift = 2,     // k_reduce_shift: unequal alignment, >= 2 tiles (ShiftArgs)
     kPlanElems = 3,     // k_reduce_elems<NATURAL = true> (ElemsArgs)
     kPlanElemsU = 4,    // k_reduce_elems<NATURAL = false> (ElemsArgs)
-    kPlanKinds = 5
+    kPlanKinds = 5,
+    // the 32-byte classes' launcher (launch_reduce_wide; HIP launch only, no direct dispatch)
+    kPlanWideTile = kPlanKinds,         // k_reduce_tile_wide: both pointers 16 B-aligned (LeanArgs, vbytes = all bytes)
+    kPlanWideElems = kPlanKinds + 1     // k_reduce_elems<NATURAL = false> (ElemsArgs)
 };
 struct LeanArgs { const char *in; char *io; uint64_t vbytes; uint64_t keep; };
 struct ElemsArgs { const char *in; char *io; uint64_t n; uint64_t stride; };
@@ -557,9 +560,13 @@ __global__ __launch_bounds__(kThreads) void k_reduce_tile_wide(const char *in, c
 // EPL: elements per lane (2 for the memory-bound ops; the compute-bound soft
 // x87 complex PROD does better with 1, more waves per element).
 // Pointers not 16 B-aligned take the element-granular kernel.
-template <class Op, class T, int EPL = 2>
-hipError_t launch_reduce_wide(const void *in_, void *io_, uint64_t count, hipStream_t s) {
-    static_assert(sizeof(T) > 16, "16-byte and smaller elements use launch_reduce");
+// The 32-byte classes' plan: the LDS-transpose tile kernel when both pointers
+// are 16 B-aligned, else the element kernel.  launch_reduce_wide launches it;
+// MPIR_Hip_plan_info reports it (Entry::wide, kernel_table.hpp).
+template <class T, int EPL>
+void plan_reduce_wide(const void *in_, void *io_, uint64_t count, ReducePlan *p) {
+    static_assert(sizeof(T) > 16, "16-byte and smaller elements use plan_reduce");
+    __builtin_memset(p, 0, sizeof *p);
     const char *in = static_cast<const char *>(in_);
     char *io = static_cast<char *>(io_);
     const uintptr_t ai = reinterpret_cast<uintptr_t>(in), ao = reinterpret_cast<uintptr_t>(io);
@@ -568,15 +575,38 @@ hipError_t launch_reduce_wide(const void *in_, void *io_, uint64_t count, hipStr
         const uint64_t nbytes = count * sizeof(T);
         uint64_t grid = (nbytes + tile - 1) / tile;
         if (grid == 0) grid = 1;
-        hipLaunchKernelGGL((k_reduce_tile_wide<Op, T, EPL>), dim3((unsigned)grid), dim3(kThreads), 0, s, in, io, nbytes,
-                           keep_for(nbytes));
-        return hipGetLastError();
+        const LeanArgs la{in, io, nbytes, keep_for(nbytes)};
+        p->kind = kPlanWideTile;
+        p->groups = grid;
+        __builtin_memcpy(p->args, &la, sizeof la);
+        p->arg_bytes = sizeof la;
+        return;
     }
     uint64_t grid = (count + kThreads - 1) / kThreads;
     if (grid > 4096) grid = 4096;
     if (grid == 0) grid = 1;
-    hipLaunchKernelGGL((k_reduce_elems<Op, T, false>), dim3((unsigned)grid), dim3(kThreads), 0, s, in, io, count,
-                       grid * kThreads);
+    const ElemsArgs ea{in, io, count, grid * kThreads};
+    p->kind = kPlanWideElems;
+    p->groups = grid;
+    __builtin_memcpy(p->args, &ea, sizeof ea);
+    p->arg_bytes = sizeof ea;
+}
+
+template <class Op, class T, int EPL = 2>
+hipError_t launch_reduce_wide(const void *in_, void *io_, uint64_t count, hipStream_t s) {
+    ReducePlan p;
+    plan_reduce_wide<T, EPL>(in_, io_, count, &p);
+    if (p.kind == kPlanWideTile) {
+        LeanArgs a;
+        __builtin_memcpy(&a, p.args, sizeof a);
+        hipLaunchKernelGGL((k_reduce_tile_wide<Op, T, EPL>), dim3((unsigned)p.groups), dim3(kThreads), 0, s, a.in, a.io,
+                           a.vbytes, a.keep);
+        return hipGetLastError();
+    }
+    ElemsArgs a;
+    __builtin_memcpy(&a, p.args, sizeof a);
+    hipLaunchKernelGGL((k_reduce_elems<Op, T, false>), dim3((unsigned)p.groups), dim3(kThreads), 0, s, a.in, a.io, a.n,
+                       a.stride);
     return hipGetLastError();
 }
 
@@ -770,10 +800,20 @@ size_t multi_lds_cap() {
     }
 }
 
-template <class Op, class T, int P, bool TREE, int U, int TH>
-hipError_t launch_combine_pu(const void *const *ins, void *out_, uint64_t count, hipStream_t s) {
-    constexpr uint32_t tile = TH * U * 16;
-    char *out = static_cast<char *>(out_);
+// The fused fold's split of `count` elements at `out`: head elements (to
+// 16 B-align out) / a 16 B vector body / tail elements when every operand is
+// naturally aligned and shares out's alignment mod 16 (vec_ok: k_combine_multi),
+// else the element kernel over all of them (k_combine_multi_elems).
+// launch_combine_pu launches it; MPIR_Hip_combine_plan_info reports it
+// (Entry::split, kernel_table.hpp).
+struct CombineSplit {
+    bool vec_ok;
+    uint64_t head;          // bytes before the vector region (at most the payload)
+    uint64_t vbytes;        // multiple of 16
+    uint32_t nhead, ntail;  // elements
+};
+template <class T>
+void combine_split(const void *const *ins, int P, const void *out, uint64_t count, CombineSplit *c) {
     const uintptr_t ao = reinterpret_cast<uintptr_t>(out);
     const uint64_t nbytes = count * sizeof(T);
     bool vec_ok = (ao % alignof(T) == 0) && (((16 - (ao & 15)) & 15) % sizeof(T) == 0);
@@ -781,21 +821,37 @@ hipError_t launch_combine_pu(const void *const *ins, void *out_, uint64_t count,
         const uintptr_t ai = reinterpret_cast<uintptr_t>(ins[j]);
         vec_ok = vec_ok && (ai % alignof(T) == 0) && (((ai ^ ao) & 15) == 0);
     }
+    c->vec_ok = vec_ok;
+    c->head = c->vbytes = 0;
+    c->nhead = c->ntail = 0;
+    if (!vec_ok) return;
+    uint64_t head = (16 - (ao & 15)) & 15;
+    if (head > nbytes) head = nbytes;
+    const uint64_t rest = nbytes - head, vbytes = rest & ~(uint64_t)15;
+    c->head = head;
+    c->vbytes = vbytes;
+    c->nhead = (uint32_t)(head / sizeof(T));
+    c->ntail = (uint32_t)((rest - vbytes) / sizeof(T));
+}
+
+template <class Op, class T, int P, bool TREE, int U, int TH>
+hipError_t launch_combine_pu(const void *const *ins, void *out_, uint64_t count, hipStream_t s) {
+    constexpr uint32_t tile = TH * U * 16;
+    char *out = static_cast<char *>(out_);
+    CombineSplit c;
+    combine_split<T>(ins, P, out_, count, &c);
     MultiArgs a;
     for (int j = 0; j < kMaxOperands; ++j) a.in[j] = j < P ? static_cast<const char *>(ins[j]) : nullptr;
-    if (vec_ok) {
-        uint64_t head = (16 - (ao & 15)) & 15;
-        if (head > nbytes) head = nbytes;
-        const uint64_t rest = nbytes - head, vbytes = rest & ~(uint64_t)15;
-        for (int j = 0; j < P; ++j) a.in[j] += head;
-        a.out = out + head;
-        a.vbytes = vbytes;
-        a.keep = keep_for(vbytes);
-        a.nhead = (uint32_t)(head / sizeof(T));
-        a.head_off = -(int64_t)head;                // head elements sit before the region start
-        a.ntail = (uint32_t)((rest - vbytes) / sizeof(T));
-        a.tail_off = (int64_t)vbytes;
-        uint64_t grid = (vbytes + tile - 1) / tile;
+    if (c.vec_ok) {
+        for (int j = 0; j < P; ++j) a.in[j] += c.head;
+        a.out = out + c.head;
+        a.vbytes = c.vbytes;
+        a.keep = keep_for(c.vbytes);
+        a.nhead = c.nhead;
+        a.head_off = -(int64_t)c.head;              // head elements sit before the region start
+        a.ntail = c.ntail;
+        a.tail_off = (int64_t)c.vbytes;
+        uint64_t grid = (c.vbytes + tile - 1) / tile;
         if (grid == 0) grid = 1;
         const size_t lds = multi_uncapped() ? 0 : multi_lds_cap<Op, T, P, TREE, U, TH>();
         hipLaunchKernelGGL((k_combine_multi<Op, T, P, TREE, U, TH>), dim3((unsigned)grid), dim3(TH), lds, s, a);

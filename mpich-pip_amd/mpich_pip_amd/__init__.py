@@ -124,7 +124,7 @@ EXPORTED_SYMBOLS = [
     "MPIR_Hip_direct_last_split", "MPIR_Hip_direct_kernarg_writes", "MPIR_Hip_direct_placement", "MPIR_Hip_build_id", "MPIR_Hip_combine_set_flags",
     "MPIR_Hip_direct_prepare", "MPIR_Hip_set_local_ranks", "MPIR_Hip_host_threads",
     "MPIR_Hip_default_rings_in_vram", "MPIR_Hip_direct_ring_location", "MPIR_Hip_set_keep_bytes",
-    "MPIR_Hip_set_keep_min_bytes",
+    "MPIR_Hip_set_keep_min_bytes", "MPIR_Hip_plan_info", "MPIR_Hip_combine_plan_info",
     # runtime subset for config 1 (include/mpi_pip.h)
     "MPI_Init", "MPI_Initialized", "MPI_Finalize", "MPI_Finalized", "MPI_Abort", "MPI_Comm_size",
     "MPI_Comm_rank", "MPI_Get_processor_name", "MPI_Wtime", "MPI_Wtick", "MPI_Barrier", "MPI_Bcast",
@@ -222,6 +222,11 @@ def load(path: str | None = None) -> ctypes.CDLL:
     for name in ("MPIR_Hip_set_keep_bytes", "MPIR_Hip_set_keep_min_bytes"):
         getattr(lib, name).argtypes = [ctypes.c_uint64]
         getattr(lib, name).restype = ctypes.c_uint64
+    lib.MPIR_Hip_plan_info.argtypes = [vp, vp, ctypes.c_uint64, i32, i32, ctypes.POINTER(ctypes.c_uint64)]
+    lib.MPIR_Hip_plan_info.restype = i32
+    lib.MPIR_Hip_combine_plan_info.argtypes = [ctypes.POINTER(vp), i32, vp, ctypes.c_uint64, i32, i32, i32,
+                                               ctypes.POINTER(ctypes.c_uint64)]
+    lib.MPIR_Hip_combine_plan_info.restype = i32
     lib.MPIR_Hip_set_local_ranks.argtypes = [i32]
     lib.MPIR_Hip_set_local_ranks.restype = i32
     lib.MPIR_Hip_host_threads.argtypes = []
@@ -324,6 +329,52 @@ def reduce_local_multi(inbufs, outbuf: int, count: int, datatype: int, op: int, 
     arr = (ctypes.c_void_p * len(inbufs))(*inbufs)
     return load().MPIX_Reduce_local_multi(arr, len(inbufs), ctypes.c_void_p(outbuf), count, datatype, op, order,
                                           ctypes.c_void_p(stream or None))
+
+
+# ---- plan introspection (include/mpir_hip_reduce.h; for tests and tools)
+# element class (enum MPIR_Hip_elem) of each datatype, as csrc/host/op_kernels.c maps them
+_ELEMS = ["I8", "U8", "I16", "U16", "I32", "U32", "I64", "U64", "F16", "F32", "F64", "CF32", "CF64", "P2INT",
+          "PFLOATINT", "PLONGINT", "PSHORTINT", "PDOUBLEINT", "F80", "CF80", "PLDOUBLEINT"]
+ELEM = {name: i + 1 for i, name in enumerate(_ELEMS)}
+ELEM_OF = {
+    "MPI_INT": "I32", "MPI_LONG": "I64", "MPI_SHORT": "I16", "MPI_UNSIGNED_SHORT": "U16", "MPI_UNSIGNED": "U32",
+    "MPI_UNSIGNED_LONG": "U64", "MPI_LONG_LONG": "I64", "MPI_UNSIGNED_LONG_LONG": "U64", "MPI_SIGNED_CHAR": "I8",
+    "MPI_UNSIGNED_CHAR": "U8", "MPI_INT8_T": "I8", "MPI_INT16_T": "I16", "MPI_INT32_T": "I32", "MPI_INT64_T": "I64",
+    "MPI_UINT8_T": "U8", "MPI_UINT16_T": "U16", "MPI_UINT32_T": "U32", "MPI_UINT64_T": "U64", "MPI_CHAR": "I8",
+    "MPI_AINT": "I64", "MPI_OFFSET": "I64", "MPI_COUNT": "I64", "MPI_FLOAT": "F32", "MPI_DOUBLE": "F64",
+    "MPI_LONG_DOUBLE": "F80", "MPIX_C_FLOAT16": "F16", "MPI_C_BOOL": "U8", "MPI_C_FLOAT_COMPLEX": "CF32",
+    "MPI_C_DOUBLE_COMPLEX": "CF64", "MPI_C_LONG_DOUBLE_COMPLEX": "CF80", "MPI_BYTE": "U8", "MPI_2INT": "P2INT",
+    "MPI_FLOAT_INT": "PFLOATINT", "MPI_LONG_INT": "PLONGINT", "MPI_SHORT_INT": "PSHORTINT",
+    "MPI_DOUBLE_INT": "PDOUBLEINT", "MPI_LONG_DOUBLE_INT": "PLDOUBLEINT",
+}
+_ELEM_BY_HANDLE = {DATATYPES[t]: ELEM[e] for t, e in ELEM_OF.items()}
+PLAN_LEAN, PLAN_FULL, PLAN_SHIFT, PLAN_ELEMS, PLAN_ELEMS_U, PLAN_WIDE_TILE, PLAN_WIDE_ELEMS = range(7)
+PLAN_NAMES = ["lean", "full", "shift", "elems", "elems_u", "wide_tile", "wide_elems"]
+COMBINE_COPY, COMBINE_FUSED_VECTOR, COMBINE_FUSED_ELEMENTS, COMBINE_ANY = range(4)
+
+
+def plan_info(inbuf: int, inoutbuf: int, count: int, datatype: int, op: int) -> dict:
+    """MPIR_Hip_plan_info: the launch plan of a device-resident MPI_Reduce_local
+    at these addresses (never dereferenced; no GPU needed).  `datatype` and `op`
+    are MPI handles.  Raises where the pair has no planned kernel."""
+    out = (ctypes.c_uint64 * 6)()
+    rc = load().MPIR_Hip_plan_info(ctypes.c_void_p(inbuf), ctypes.c_void_p(inoutbuf), count, op & 0xFF,
+                                   _ELEM_BY_HANDLE[datatype], out)
+    if rc:
+        raise LookupError(f"MPIR_Hip_plan_info: {rc}")
+    return dict(zip(("kind", "groups", "nhead", "ntail", "vbytes", "keep"), (int(v) for v in out)))
+
+
+def combine_plan_info(inbufs, outbuf: int, count: int, datatype: int, op: int, order: int) -> dict:
+    """MPIR_Hip_combine_plan_info: the path of a fold of device buffers at these
+    addresses (never dereferenced; no GPU needed)."""
+    arr = (ctypes.c_void_p * len(inbufs))(*inbufs)
+    out = (ctypes.c_uint64 * 4)()
+    rc = load().MPIR_Hip_combine_plan_info(arr, len(inbufs), ctypes.c_void_p(outbuf), count, op & 0xFF,
+                                           _ELEM_BY_HANDLE[datatype], order, out)
+    if rc:
+        raise LookupError(f"MPIR_Hip_combine_plan_info: {rc}")
+    return dict(zip(("path", "passes", "nhead", "ntail"), (int(v) for v in out)))
 
 
 MPIX_HIP_ALG_AUTO = 0

@@ -7,6 +7,11 @@ allgather -- runs end to end on one MI355X.  The RCCL communicator differs
 only in its transport (grouped ncclSend/ncclRecv) and needs one GPU per rank.
 Expected bytes: oracle/schedules.py, the reference schedules run step by step
 on the CPU oracle.  Bit-exact (complex NaN payloads excepted).
+
+Not tested here: two pipelined collectives back to back on a caller's stream
+(ADVICE.md round 6).  The loopback transport synchronises the stream after
+every group, so on one GPU that case passes whether or not the ordering
+across the two calls is right; it needs the RCCL transport.
 """
 import threading
 
@@ -502,6 +507,118 @@ def test_pipelined_reference_order(mpi, orc, cuda, t, op, p, kind, monkeypatch):
                 continue
             got = recv[r].cpu().numpy()
             assert same(got, want[r], t), f"rank {r}: {np.count_nonzero(got != want[r])} bytes differ"
+    finally:
+        for c in comms:
+            mpi.comm_free(c)
+
+
+PIPE_EDGES = [("MPI_FLOAT", "MPI_SUM"), ("MPIX_C_FLOAT16", "MPI_SUM")]
+
+
+def _pipe_counts(p, esz):
+    """Irregular Reduce_scatter counts for 64 KiB chunks (4-byte units, scaled to
+    esz): a block of several chunks and a ragged end, a zero count, a block
+    shorter than one chunk (its later chunks are empty), and counts larger than
+    their displacement (ranks 2 and p - 1: in place, the own block overlaps the
+    output and is staged); >= 524288 bytes in all, so the pairwise schedule runs."""
+    units = [5000, 0, 160003] if p == 3 else [5000, 0, 40001, 70001, 1, 33000, 16384, 200003]
+    counts = [u * (4 // esz) for u in units]
+    disps = [sum(counts[:i]) for i in range(p)]
+    assert sum(counts) * esz >= 524288 and max(counts) * esz >= 4 * 65536 and 0 < counts[0] * esz < 65536
+    assert 0 < disps[-1] < counts[-1] and 0 < disps[2] < counts[2]
+    return counts
+
+
+@pytest.mark.parametrize("t,op", PIPE_EDGES, ids=[f"{t}-{o}" for t, o in PIPE_EDGES])
+@pytest.mark.parametrize("p", [3, 8])
+@pytest.mark.parametrize("kind", ["allreduce_inplace", "reduce_scatter_block_inplace", "reduce_every_root",
+                                  "reduce_scatter_irregular", "reduce_scatter_irregular_inplace",
+                                  "allreduce_rechunked"])
+def test_pipelined_reference_order_edges(mpi, orc, cuda, t, op, p, kind, monkeypatch):
+    """The pipelined exchange (on by default) where test_pipelined_reference_order
+    does not go: MPI_IN_PLACE (Allreduce, Reduce_scatter_block, Reduce at the
+    root), MPIX_Reduce_scatter_hip with irregular counts out of place and in
+    place (_pipe_counts), Reduce at every root -- so each rank the pre-fold
+    excludes at p = 3 is the root once, out of place and in place -- and blocks
+    of 64 KiB at MPIR_CVAR_DEVICE_COLL_PIPELINE_KB=1, which pipe_chunks cuts into
+    more than its 16 chunks and re-sizes (chunks rounded up to 256 B, a ragged
+    last one).  Same oracle and comparison as test_pipelined_reference_order."""
+    from oracle import schedules as S
+    rechunk = kind == "allreduce_rechunked"
+    monkeypatch.setenv("MPIR_CVAR_DEVICE_COLL_PIPELINE_KB", "1" if rechunk else "64")
+    torch = cuda
+    esz = T.elem_size(t)
+    dt, o = mpi.DATATYPES[t], mpi.OPS[op]
+    REF = mpi.MPIX_HIP_ALG_REFERENCE_ORDER
+    rng = np.random.default_rng(31 * p + len(kind))
+    comms = mpi.comm_create_loopback(p)
+
+    def check(got, want, what):
+        assert same(got, want, t), f"{kind} p={p} {what}: {np.count_nonzero(got != want)} bytes differ"
+
+    try:
+        if kind in ("allreduce_inplace", "allreduce_rechunked"):
+            pof2 = 1 << (p.bit_length() - 1)
+            count = pof2 * (65536 // esz) + 5 if rechunk else (1 << 19) + 7
+            xs = [T.to_bytes(T.gen(t, count, rng, op)) for _ in range(p)]
+            want = S.allreduce_smp_auto(xs, count, esz, dt, o)
+            for inplace in ((True,) if not rechunk else (False, True)):
+                send = [torch.from_numpy(x.copy()).cuda() for x in xs]
+                recv = [s.clone() if inplace else torch.zeros_like(s) for s in send]
+                torch.cuda.synchronize()
+                run_ranks(lambda r: _ok(mpi, mpi.allreduce(mpi.MPI_IN_PLACE if inplace else send[r].data_ptr(),
+                                                           recv[r].data_ptr(), count, dt, o, comms[r], REF)), p)
+                torch.cuda.synchronize()
+                for r in range(p):
+                    check(recv[r].cpu().numpy(), want, f"inplace={inplace} rank {r}")
+        elif kind == "reduce_scatter_block_inplace":
+            count = (1 << 17) + 5
+            xs = [T.to_bytes(T.gen(t, count * p, rng, op)) for _ in range(p)]
+            want = S.reduce_scatter_block_auto(xs, count, esz, dt, o)
+            recv = [torch.from_numpy(x.copy()).cuda() for x in xs]
+            torch.cuda.synchronize()
+            run_ranks(lambda r: _ok(mpi, mpi.reduce_scatter_block(mpi.MPI_IN_PLACE, recv[r].data_ptr(), count, dt, o,
+                                                                  comms[r], REF)), p)
+            torch.cuda.synchronize()
+            for r in range(p):
+                check(recv[r][:count * esz].cpu().numpy(), want[r], f"rank {r}")
+        elif kind == "reduce_every_root":
+            count = (1 << 19) + 7
+            xs = [T.to_bytes(T.gen(t, count, rng, op)) for _ in range(p)]
+            send = [torch.from_numpy(x.copy()).cuda() for x in xs]
+            keep = [s.clone() for s in send]
+            for root in range(p):
+                want = S.reduce_auto(xs, count, esz, dt, o, root)
+                for inplace in (False, True):
+                    rbuf = send[root].clone() if inplace else torch.zeros_like(send[root])
+                    torch.cuda.synchronize()
+
+                    def rank(r):
+                        sb = mpi.MPI_IN_PLACE if (inplace and r == root) else send[r].data_ptr()
+                        _ok(mpi, mpi.reduce(sb, rbuf.data_ptr() if r == root else 0, count, dt, o, root, comms[r], REF))
+
+                    run_ranks(rank, p)
+                    torch.cuda.synchronize()
+                    check(rbuf.cpu().numpy(), want, f"root {root} inplace={inplace}")
+                    for r in range(p):
+                        assert torch.equal(send[r], keep[r]), f"root {root}: rank {r} sendbuf modified"
+        else:
+            inplace = kind.endswith("_inplace")
+            counts = _pipe_counts(p, esz)
+            xs = [T.to_bytes(T.gen(t, sum(counts), rng, op)) for _ in range(p)]
+            want = S.reduce_scatter_auto(xs, counts, esz, dt, o)
+            send = [torch.from_numpy(x.copy()).cuda() for x in xs]
+            recv = [s.clone() if inplace else torch.zeros(max(1, c) * esz + 64, dtype=torch.uint8, device="cuda")
+                    for s, c in zip(send, counts)]
+            torch.cuda.synchronize()
+            run_ranks(lambda r: _ok(mpi, mpi.reduce_scatter(mpi.MPI_IN_PLACE if inplace else send[r].data_ptr(),
+                                                            recv[r].data_ptr(), counts, dt, o, comms[r], REF)), p)
+            torch.cuda.synchronize()
+            for r in range(p):
+                check(recv[r][:counts[r] * esz].cpu().numpy(), want[r], f"counts {counts} rank {r}")
+                if not inplace:
+                    assert not recv[r][counts[r] * esz:].any(), f"rank {r}: wrote past its block"
+                    assert torch.equal(send[r], torch.from_numpy(xs[r]).cuda()), f"rank {r} sendbuf modified"
     finally:
         for c in comms:
             mpi.comm_free(c)

@@ -54,6 +54,16 @@ def back(t, offset, n):
     return t[offset:offset + n].cpu().numpy()
 
 
+def guards_zero(t, offset, n, what):
+    """dev() pads every allocation with zero bytes (`offset` before the payload,
+    256 after): a kernel that writes outside its operand shows here."""
+    import torch
+    torch.cuda.synchronize()
+    whole = t.cpu().numpy()
+    bad = np.nonzero(whole[:offset])[0].tolist() + (offset + n + np.nonzero(whole[offset + n:])[0]).tolist()
+    assert not bad, f"{what}: bytes outside the payload [{offset}, {offset + n}) written at {bad[:8]}"
+
+
 def explain(got, want, a, b, esz, limit=6):
     g = got.reshape(-1, esz)
     w = want.reshape(-1, esz)
@@ -105,6 +115,8 @@ def run_pair(mpi, orc, torch, op, t, n, seed, off_in=0, off_io=0):
     got = back(tio, off_io, a.size)
     assert mpi.error_class(rc) == rc_o, (op, t, rc, rc_o)
     assert np.array_equal(back(tin, off_in, b.size), b), "inbuf modified"
+    guards_zero(tio, off_io, a.size, f"{op} {t} n={n} off=({off_in},{off_io}) inoutbuf")
+    guards_zero(tin, off_in, b.size, f"{op} {t} n={n} off=({off_in},{off_io}) inbuf")
     if not same(got, want, t):
         pytest.fail(f"{op} {t} n={n} off=({off_in},{off_io}):\n" + explain(got, want, a, b, T.elem_size(t)))
 
@@ -812,12 +824,14 @@ def run_pair_mixed(mpi, orc, torch, op, t, n, seed, host_side, pinned=False, off
         rc = mpi.reduce_local(pin, pio, n, mpi.DATATYPES[t], mpi.OPS[op])
         got = back(tio, off_dev, a.size)
         assert np.array_equal(host_back(hin, b.size), b), "inbuf modified"
+        guards_zero(tio, off_dev, a.size, f"mixed {op} {t} n={n} off=({off_host},{off_dev}) inoutbuf")
     else:
         tin, pin = dev(torch, b, off_dev)
         hio, pio = host(a)
         rc = mpi.reduce_local(pin, pio, n, mpi.DATATYPES[t], mpi.OPS[op])
         got = host_back(hio, a.size)
         assert np.array_equal(back(tin, off_dev, b.size), b), "inbuf modified"
+        guards_zero(tin, off_dev, b.size, f"mixed {op} {t} n={n} off=({off_host},{off_dev}) inbuf")
     assert mpi.error_class(rc) == rc_o, (op, t, rc, rc_o)
     if not same(got, want, t):
         pytest.fail(f"mixed ({host_side} on host, pinned={pinned}) {op} {t} n={n} off=({off_host},{off_dev}):\n"

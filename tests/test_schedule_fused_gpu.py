@@ -358,3 +358,211 @@ def test_two_operand_fold_large_blocks(mpi, orc, cuda, t, order, nbytes):
     got = out.cpu().numpy().view(np.uint8)
     assert not got[:esz].any(), "wrote before the output"
     assert np.array_equal(got[esz:], acc[0]), f"{np.count_nonzero(got[esz:] != acc[0])} bytes differ"
+
+
+# ---------------------------------------------------------------------------
+# The fused fold's launch-plan edges.  Every case asserts the path
+# MPIR_Hip_combine_plan_info reports (the launch's own split) before it runs, so
+# a case aimed at k_combine_multi_elems cannot pass on k_combine_multi.  Data,
+# reference and comparison as in test_every_pair_fused_matches_stepwise_fold: the
+# oracle folds one MPIR_Reduce_local step at a time, compared with same(); every
+# allocation is zero around its payload and checked after the call.
+# ---------------------------------------------------------------------------
+ELEMS_STRIDE = 2 * 1048576 + 4099       # k_combine_multi_elems: 4096 workgroups, 1,048,576 elements per stride
+ANY_STRIDE = 2 * 2097152 + 4099         # k_combine_any: 8192 workgroups, 2,097,152 elements per stride
+
+
+def _align_of(t):
+    """Alignment of the device type of MPI type t (reduce_ops.hpp)."""
+    if t in ("MPI_LONG_DOUBLE", "MPI_C_LONG_DOUBLE_COMPLEX", "MPI_LONG_DOUBLE_INT"):
+        return 16
+    if t in T.CPLX:
+        return T.elem_size(t) // 2
+    if t in T.PAIRS:
+        return {"MPI_2INT": 4, "MPI_FLOAT_INT": 4, "MPI_LONG_INT": 8, "MPI_SHORT_INT": 4, "MPI_DOUBLE_INT": 8}[t]
+    return T.elem_size(t)
+
+
+def _fold(orc, xs, count, dt, o, order):
+    acc = [x.copy() for x in xs]
+    n = len(xs)
+    if order == "TREE":
+        step = 1
+        while step < n:
+            for j in range(0, n, 2 * step):
+                assert orc.reduce_local(acc[j + step], acc[j], count, dt, o, check=False) == 0
+            step *= 2
+    else:
+        for j in range(1, n):
+            assert orc.reduce_local(acc[j], acc[0], count, dt, o, check=False) == 0
+    return acc[0]
+
+
+def _has_fused(mpi, t, op):
+    """Whether (op, t) has a fused fold: the path of an aligned fold of two (made-up addresses)."""
+    a = 1 << 32
+    return mpi.combine_plan_info([a, a + 4096], a + 8192, 16, mpi.DATATYPES[t], mpi.OPS[op],
+                                 mpi.MPIX_ORDER_CHAIN)["path"] == mpi.COMBINE_FUSED_VECTOR
+
+
+def _run_fold(mpi, torch, xs, want, t, op, order, offs, off_out, path, alias=False):
+    """Operand j at byte offset offs[j] of its own zeroed allocation, the output
+    at off_out of another (or operand 0 itself: alias); returns the plan info."""
+    esz = T.elem_size(t)
+    nb = xs[0].size
+    count = nb // esz
+    dev = []
+    for x, off in zip(xs, offs):
+        d = torch.zeros(nb + off + 64, dtype=torch.uint8, device="cuda")
+        assert d.data_ptr() % 16 == 0
+        d[off:off + nb].copy_(torch.from_numpy(x))
+        dev.append(d)
+    if alias:
+        out, off_out = dev[0], offs[0]
+    else:
+        out = torch.zeros(nb + off_out + 64, dtype=torch.uint8, device="cuda")
+    ptrs = [d.data_ptr() + off for d, off in zip(dev, offs)]
+    ordv = mpi.MPIX_ORDER_TREE if order == "TREE" else mpi.MPIX_ORDER_CHAIN
+    what = f"{op} {t} {order}{len(xs)} count={count} in=+{list(offs)} out=+{off_out}{' (= in[0])' if alias else ''}"
+    info = mpi.combine_plan_info(ptrs, out.data_ptr() + off_out, count, mpi.DATATYPES[t], mpi.OPS[op], ordv)
+    assert info["path"] == path, f"{what}: aimed at path {path}, the planner says {info}"
+    torch.cuda.synchronize()
+    rc = mpi.reduce_local_multi(ptrs, out.data_ptr() + off_out, count, mpi.DATATYPES[t], mpi.OPS[op], ordv)
+    assert rc == 0, f"{what}: {mpi.error_string(rc)}"
+    torch.cuda.synchronize()
+    whole = out.cpu().numpy()
+    got = whole[off_out:off_out + nb]
+    assert same(got, want, t), f"{what}: {np.count_nonzero(got != want)} bytes differ"
+    assert not whole[:off_out].any() and not whole[off_out + nb:].any(), f"{what}: wrote outside the output"
+    for j in range(1 if alias else 0, len(xs)):
+        w = dev[j].cpu().numpy()
+        assert np.array_equal(w[offs[j]:offs[j] + nb], xs[j]) and not w[:offs[j]].any() and \
+            not w[offs[j] + nb:].any(), f"{what}: operand {j} or its surroundings written"
+    return info
+
+
+@pytest.mark.parametrize("op,t", EVERY, ids=[f"{o}-{t}" for o, t in EVERY])
+def test_every_pair_misaligned_operands_element_fold(mpi, orc, cuda, op, t):
+    """Operands that do not share the output's alignment mod 16, or are not
+    naturally aligned, take the fused fold's element kernel
+    (k_combine_multi_elems): every pair with a fused fold, TREE of 2, 4, 8 and
+    CHAIN of 2, 3, 5, 8 at count 3001, with all operands off the output, one
+    operand off, every operand at another offset, every pointer one byte off its
+    natural alignment, and CHAIN into its own first operand.  (The 32-byte
+    classes have no fused fold: the same operands go through k_combine_any.)"""
+    torch = cuda
+    esz, align = T.elem_size(t), _align_of(t)
+    dt, o = mpi.DATATYPES[t], mpi.OPS[op]
+    path = mpi.COMBINE_FUSED_ELEMENTS if _has_fused(mpi, t, op) else mpi.COMBINE_ANY
+    # the offsets mod 16 a naturally aligned operand can have; a 16 B-aligned type
+    # has only 0, and is misaligned by 8 instead
+    offs = [k * align for k in range(16 // align)] if align < 16 else [0, 8]
+    count = 3001
+    for k, (n, order) in enumerate(((2, "TREE"), (4, "TREE"), (8, "TREE"), (2, "CHAIN"), (3, "CHAIN"), (5, "CHAIN"),
+                                    (8, "CHAIN"))):
+        rng = np.random.default_rng(77 * n + k)
+        xs = [T.to_bytes(T.gen(t, count, rng, op)) for _ in range(n)]
+        want = _fold(orc, xs, count, dt, o, order)
+        variants = [([offs[1]] * n, offs[0], False),                                     # all operands off the output
+                    ([offs[-1] if j == n // 2 else 0 for j in range(n)], 0, False),      # one operand off
+                    ([offs[(j + 1) % len(offs)] for j in range(n)], offs[0], False)]     # each at another offset
+        if esz >= 2:
+            variants.append(([1] * n, 1, False))                                         # unnatural, all alike
+        if order == "CHAIN":
+            variants.append(([offs[-1] if j == n - 1 else 0 for j in range(n)], 0, True))   # out == in[0]
+        for ins, off_out, alias in variants:
+            _run_fold(mpi, torch, xs, want, t, op, order, ins, off_out, path, alias)
+
+
+# one pair per element size (16 B: the class of 8 B alignment, which may sit at offset 8 too)
+VEC_PAIRS = [("MPI_BXOR", "MPI_UNSIGNED_CHAR"), ("MPI_SUM", "MPIX_C_FLOAT16"), ("MPI_SUM", "MPI_FLOAT"),
+             ("MPI_MAX", "MPI_DOUBLE"), ("MPI_SUM", "MPI_C_DOUBLE_COMPLEX")]
+
+
+class _keep_min:
+    """MPIR_Hip_set_keep_min_bytes(0) for the "sc1" runs: every result up to 64 MiB
+    is then stored sc1 instead of nt."""
+
+    def __init__(self, mpi, store):
+        self.lib, self.on = mpi.load(), store == "sc1"
+
+    def __enter__(self):
+        self.prev = self.lib.MPIR_Hip_set_keep_min_bytes(0) if self.on else None
+
+    def __exit__(self, *exc):
+        if self.on:
+            self.lib.MPIR_Hip_set_keep_min_bytes(self.prev)
+        return False
+
+
+@pytest.mark.parametrize("store", ["nt", "sc1"])
+@pytest.mark.parametrize("op,t", VEC_PAIRS, ids=[f"{o}-{t}" for o, t in VEC_PAIRS])
+def test_fused_vector_path_every_head_and_tail(mpi, orc, cuda, op, t, store):
+    """The fused vector kernel (k_combine_multi) with every head size the type
+    allows (operands and output alike at esz, 2 esz, ... < 16, and at 0) and
+    every tail size, over one full tile and a ragged second one, on both kernel
+    shapes (256 x 4 vectors: TREE4; 1024 x 1: CHAIN5); again with sc1 stores."""
+    torch = cuda
+    esz = T.elem_size(t)
+    dt, o = mpi.DATATYPES[t], mpi.OPS[op]
+    per = 16 // esz
+    base = (16384 + 5 * 16) // esz
+    with _keep_min(mpi, store):
+        for n, order in ((4, "TREE"), (5, "CHAIN")):
+            rng = np.random.default_rng(n)
+            full = [T.to_bytes(T.gen(t, base + per, rng, op)) for _ in range(n)]
+            for extra in range(per):
+                count = base + extra
+                xs = [x[:count * esz] for x in full]
+                want = _fold(orc, xs, count, dt, o, order)
+                for off in range(0, 16, esz):
+                    info = _run_fold(mpi, torch, xs, want, t, op, order, [off] * n, off, mpi.COMBINE_FUSED_VECTOR)
+                    head = -off % 16 // esz
+                    assert (info["nhead"], info["ntail"]) == (head, (count - head) % per), (off, count, info)
+
+
+@pytest.mark.parametrize("store", ["nt", "sc1"])
+@pytest.mark.parametrize("op,t", VEC_PAIRS, ids=[f"{o}-{t}" for o, t in VEC_PAIRS])
+def test_fused_vector_path_tiny_counts(mpi, orc, cuda, op, t, store):
+    """Counts smaller than the head (the head is clamped to the payload and the
+    vector region is empty: a grid of one workgroup that only combines head
+    elements), and exactly one vector with and without a head."""
+    torch = cuda
+    esz = T.elem_size(t)
+    dt, o = mpi.DATATYPES[t], mpi.OPS[op]
+    per = 16 // esz
+    with _keep_min(mpi, store):
+        for n, order in ((2, "TREE"), (8, "TREE"), (3, "CHAIN"), (8, "CHAIN")):
+            for count, off in sorted({(c, esz % 16) for c in (1, 2, per - 1) if c >= 1} | {(per, 0), (per, esz % 16)}):
+                rng = np.random.default_rng([n, count, off])
+                xs = [T.to_bytes(T.gen(t, count, rng, op)) for _ in range(n)]
+                want = _fold(orc, xs, count, dt, o, order)
+                info = _run_fold(mpi, torch, xs, want, t, op, order, [off] * n, off, mpi.COMBINE_FUSED_VECTOR)
+                head = min(-off % 16 // esz, count)
+                assert info["nhead"] == head and info["ntail"] == (count - head) % per, (count, off, info)
+
+
+STRIDE_FOLDS = [("MPI_SUM", "MPI_FLOAT", "TREE", 4, ELEMS_STRIDE, 4, "elements"),
+                ("MPI_SUM", "MPI_FLOAT", "CHAIN", 5, ELEMS_STRIDE, 4, "elements"),
+                ("MPI_LAND", "MPI_INT", "CHAIN", 3, ANY_STRIDE, 0, "vector"),
+                ("MPI_MINLOC", "MPI_2INT", "TREE", 16, ANY_STRIDE, 0, "any"),
+                ("MPI_MAXLOC", "MPI_LONG_DOUBLE_INT", "CHAIN", 2, 2097152 + 4099, 0, "any")]
+
+
+@pytest.mark.parametrize("op,t,order,n,count,off,path", STRIDE_FOLDS,
+                         ids=[f"{o}-{t}-{r}{n}-{p}" for o, t, r, n, _, _, p in STRIDE_FOLDS])
+def test_fold_grid_stride_loops_take_another_stride(mpi, orc, cuda, op, t, order, n, count, off, path):
+    """The element-granular folds cap their grids (k_combine_multi_elems at 4096
+    workgroups, k_combine_any at 8192): counts past two strides, operand 0 `off`
+    bytes off the output for the fused fold's element kernel.  MPI_LAND over
+    MPI_INT has a fused fold (reg_multi_logic.hip), so its CHAIN of 3 at this
+    count runs the vector kernel, as the planner says; the CHAIN branch of
+    k_combine_any is reached with a class that has no fused fold
+    (MPI_LONG_DOUBLE_INT, one stride and a ragged second)."""
+    torch = cuda
+    dt, o = mpi.DATATYPES[t], mpi.OPS[op]
+    rng = np.random.default_rng(count + n)
+    xs = [T.to_bytes(T.gen(t, count, rng, op)) for _ in range(n)]
+    want = _fold(orc, xs, count, dt, o, order)
+    want_path = {"elements": mpi.COMBINE_FUSED_ELEMENTS, "vector": mpi.COMBINE_FUSED_VECTOR, "any": mpi.COMBINE_ANY}[path]
+    _run_fold(mpi, torch, xs, want, t, op, order, [off] + [0] * (n - 1), 0, want_path)
