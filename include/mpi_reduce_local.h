@@ -238,6 +238,36 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_stream(const void *inbuf, void *inoutbuf,
 #define MPIX_ORDER_CHAIN 1
 MPICH_API_PUBLIC int MPIX_Reduce_local_multi(const void *const *inbufs, int n, void *outbuf, int count,
                             MPI_Datatype datatype, MPI_Op op, int order, void *hip_stream);
+/* Batched local reduction: nsegs independent MPI_Reduce_local's under one
+ * (op, datatype) in one kernel launch -- a bucket of gradient tensors, the
+ * per-block combines of an accumulate on a derived target type, the blocks of
+ * a ragged reduce-scatter, the sub-ranges of a schedule step.  Each segment's
+ * result is bit-identical to MPI_Reduce_local(inbuf, inoutbuf, count, ...).
+ *   hip_stream NULL: synchronous on the calling thread's library stream, every
+ *       result complete on return; otherwise enqueued on that stream without
+ *       waiting (the segment table is copied into the launch: `segs` may be
+ *       reused at once).
+ *   Builtin ops and basic types, each segment validated as MPI_Reduce_local
+ *       validates (MPI_REPLACE, MPI_NO_OP, null and invalid ops: MPI_ERR_OP;
+ *       inbuf == inoutbuf: MPI_ERR_BUFFER under MPIR_CVAR_COLL_ALIAS_CHECK;
+ *       MPI_IN_PLACE: MPI_ERR_BUFFER); user ops give MPI_ERR_OP (they run on
+ *       the host), MPI_LAND / MPI_LOR on floating types MPI_ERR_OP.
+ *   nsegs == 0 succeeds; nsegs < 0, or segs == NULL with nsegs > 0, is
+ *       MPI_ERR_ARG.  A segment with count == 0 is skipped and its pointers
+ *       are not looked at; count < 0 is MPI_ERR_COUNT.
+ *   Every non-empty segment's two buffers must be device-resident, all on one
+ *       device (else MPI_ERR_BUFFER).
+ *   Everything is validated and classified before the first launch: a call
+ *       that returns an error has modified nothing.
+ *   Segments may share or overlap inbufs.  Two segments whose inoutbuf ranges
+ *       overlap, or an inbuf overlapping another segment's inoutbuf, are
+ *       undefined (not checked): the segments run concurrently.
+ *   A batch with exactly one non-empty segment is the single call.
+ * More non-empty segments than fit one launch's kernel arguments (127) run as
+ * back-to-back launches on the same stream. */
+typedef struct MPIX_Reduce_local_seg { const void *inbuf; void *inoutbuf; int count; } MPIX_Reduce_local_seg;
+MPICH_API_PUBLIC int MPIX_Reduce_local_batch(const MPIX_Reduce_local_seg *segs, int nsegs,
+                            MPI_Datatype datatype, MPI_Op op, void *hip_stream);
 MPICH_API_PUBLIC int MPIX_Reduce_local_set_errhandler(MPI_Errhandler errhandler);
 MPICH_API_PUBLIC int MPIX_Reduce_local_get_errhandler(MPI_Errhandler * errhandler);
 

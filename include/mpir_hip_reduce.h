@@ -111,6 +111,38 @@ int MPIR_Hip_plan_info(const void *inbuf, const void *inoutbuf, uint64_t count, 
 int MPIR_Hip_combine_plan_info(const void *const *inbufs, int n, const void *outbuf, uint64_t count, int op, int elem,
                                int order, uint64_t out[4]);
 
+/* Batched reduction: io[i] = op(io[i], in[i]), i < count, for each of nsegs
+ * independent segments under one (op, elem), in one kernel launch per
+ * MPIR_Hip_batch_plan_info's "max segments per launch" non-empty segments
+ * (back-to-back launches on the same stream beyond that).  Each segment's
+ * result is bit-identical to MPIR_Hip_reduce on it.  Every non-empty segment's
+ * two buffers must be device-resident, all on one device (else
+ * MPIR_HIP_EBUFFER); every pointer is classified before the first launch, so a
+ * call that fails has written nothing.  count == 0 segments are skipped, their
+ * pointers never looked at.  Segments may share or overlap inputs; overlapping
+ * outputs, or an input overlapping another segment's output, are undefined.
+ * A batch with exactly one non-empty segment is MPIR_Hip_reduce on it.
+ * hip_stream / sync as for MPIR_Hip_reduce.  The segment table travels in the
+ * kernel arguments: `segs` may be reused as soon as the call returns. */
+typedef struct { const void *in; void *io; uint64_t count; } MPIR_Hip_seg;
+int MPIR_Hip_reduce_batch(const MPIR_Hip_seg *segs, int nsegs, int op, int elem, void *hip_stream, int sync);
+
+/* For tests and tools: the launches MPIR_Hip_reduce_batch would make for
+ * device segments at these addresses, from the same planner the launch calls
+ * (host arithmetic on the pointer values only).  out = {launches, workgroups
+ * over all launches, tile-path segments, element-path segments, empty
+ * segments, max segments per launch}; seg_kind / seg_groups (each nsegs
+ * entries, or NULL) receive every segment's path below and its workgroups.  A
+ * launch also closes before its workgroups pass MPIR_HIP_BATCH_MAX_GROUPS.
+ * MPIR_HIP_ENOKERNEL for REPLACE and for pairs with no kernel. */
+#define MPIR_HIP_BATCH_SEG_EMPTY  0   /* count == 0: skipped */
+#define MPIR_HIP_BATCH_SEG_TILE   1   /* naturally aligned, equal offsets mod 16: the 16 KiB tile grid */
+#define MPIR_HIP_BATCH_SEG_ELEMS  2   /* any other alignment, and the 32-byte classes: element runs */
+#define MPIR_HIP_BATCH_SEG_SINGLE 3   /* the only non-empty segment: MPIR_Hip_reduce's own plan */
+#define MPIR_HIP_BATCH_MAX_GROUPS (1ull << 23)
+int MPIR_Hip_batch_plan_info(const MPIR_Hip_seg *segs, int nsegs, int op, int elem,
+                             uint64_t out[6], uint32_t *seg_kind, uint32_t *seg_groups);
+
 /* Flags for the calling thread's later MPIR_Hip_combine calls; returns the
  * previous flags.  MPIR_HIP_COMBINE_UNCAPPED: the fused folds run without the
  * LDS reservation that caps a CU at one (P >= 5) or three (P = 3, 4) of their

@@ -51,6 +51,7 @@ void direct_test_fail_probe();
 void direct_placement(int dev, int out[5]);
 Entry g_table[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
+BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 
 // Results of at most this many bytes are stored sc1 (into the Infinity Cache)
 // rather than nt: MPIR_CVAR_REDUCE_LOCAL_KEEP_MB (0 = every store nt), default
@@ -905,6 +906,37 @@ Loc classify(const void *p, int *dev, bool reuse = true, bool *kept = nullptr) {
     return l;
 }
 
+// classify() for the many pointers of one batch.  Its segments usually sit in
+// a few allocations (the blocks of one receive buffer, a bucket's tensors in
+// one flat buffer), and the query is most of a small batch's host time (two per
+// segment, 24-66 ns each): a pointer inside the device allocation that answered
+// last -- HSA's own base and size for it -- is that device's without a query.
+// Only device answers are kept, for the length of one call.
+struct DeviceSpan {
+    uintptr_t lo = 0, hi = 0;
+    int dev = -1;
+};
+Loc classify_in_span(const void *p, int *dev, DeviceSpan &span) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    if (a >= span.lo && a < span.hi) {
+        *dev = span.dev;
+        return LOC_DEVICE;
+    }
+    const Loc l = classify(p, dev);
+    if (l != LOC_DEVICE) return l;
+    hsa_amd_pointer_info_t info;
+    info.size = sizeof info;
+    if (hsa_amd_pointer_info(p, &info, nullptr, nullptr, nullptr) != HSA_STATUS_SUCCESS) return l;
+    if (info.type != HSA_EXT_POINTER_TYPE_HSA && info.type != HSA_EXT_POINTER_TYPE_HSA_VMEM) return l;
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(info.agentBaseAddress);
+    if (lo && a >= lo && a - lo < info.sizeInBytes && agent_device(info.agentOwner) == *dev) {
+        span.lo = lo;
+        span.hi = lo + info.sizeInBytes;
+        span.dev = *dev;
+    }
+    return l;
+}
+
 bool verdict_reusable(uint64_t bytes) { return bytes <= mixed_max_bytes() && bytes <= host_max_bytes(); }
 
 // devices visible to this process (0 on a CPU-only rank: host operands are
@@ -1112,6 +1144,66 @@ int chain_passes(const void *const *inbufs, int n, const void *outbuf, F fn) {
         acc = outbuf;
     }
     return passes;
+}
+
+// The launches of a batch (MPIR_Hip_reduce_batch makes them,
+// MPIR_Hip_batch_plan_info counts them): the non-empty segments in order, each
+// at the first workgroup its predecessors leave it; a launch closes at
+// kBatchMaxSegs descriptors or before its workgroups pass kBatchMaxGroups.
+// emit(args, groups) per launch, until it returns false.  seg_kind / seg_groups
+// (or null): every segment's path and workgroups.  totals = {launches,
+// workgroups, tile segments, element segments, empty segments}.
+template <class F>
+void batch_launches(const BatchEntry &en, const MPIR_Hip_seg *segs, int nsegs, uint32_t *seg_kind, uint32_t *seg_groups,
+                    uint64_t totals[5], F emit) {
+    BatchArgs a;
+    memset(&a, 0, sizeof a);
+    uint64_t groups = 0;
+    for (int k = 0; k < 5; ++k) totals[k] = 0;
+    auto flush = [&]() {
+        if (!a.nsegs) return true;
+        ++totals[0];
+        totals[1] += groups;
+        const bool go = emit(a, groups);
+        memset(&a, 0, sizeof a);
+        groups = 0;
+        return go;
+    };
+    for (int i = 0; i < nsegs; ++i) {
+        if (segs[i].count == 0) {
+            ++totals[4];
+            if (seg_kind) seg_kind[i] = MPIR_HIP_BATCH_SEG_EMPTY;
+            if (seg_groups) seg_groups[i] = 0;
+            continue;
+        }
+        int tile = 0;
+        const uint64_t g = en.groups(segs[i].in, segs[i].io, segs[i].count, &tile);
+        ++totals[tile ? 2 : 3];
+        if (seg_kind) seg_kind[i] = tile ? MPIR_HIP_BATCH_SEG_TILE : MPIR_HIP_BATCH_SEG_ELEMS;
+        if (seg_groups) seg_groups[i] = (uint32_t)g;
+        if ((a.nsegs == (uint32_t)kBatchMaxSegs || groups + g > kBatchMaxGroups) && !flush()) return;
+        a.seg[a.nsegs++] = BatchSeg{static_cast<const char *>(segs[i].in), static_cast<char *>(segs[i].io),
+                                    segs[i].count, groups};
+        groups += g;
+    }
+    flush();
+}
+
+// the batch's only non-empty segment, or -1 if it has none or several
+int batch_single(const MPIR_Hip_seg *segs, int nsegs) {
+    int one = -1;
+    for (int i = 0; i < nsegs; ++i)
+        if (segs[i].count) {
+            if (one >= 0) return -1;
+            one = i;
+        }
+    return one;
+}
+
+bool batch_args_ok(const MPIR_Hip_seg *segs, int nsegs, int op, int elem) {
+    if (nsegs < 0 || (nsegs > 0 && !segs)) return false;
+    if (op <= 0 || op >= MPIR_HIP_NOPS || elem <= 0 || elem >= MPIR_HIP_NELEMS) return false;
+    return g_batch[op][elem].launch && g_batch[op][elem].groups;
 }
 
 }  // namespace
@@ -1506,6 +1598,84 @@ int MPIR_Hip_reduce(const void *inbuf, void *inoutbuf, uint64_t count, int op, i
             rc = drain(j);
     if (rc == MPIR_HIP_OK) rc = wait_stream_block(comp);
     if (rc == MPIR_HIP_OK) rc = wait_stream_block(down);
+    if (cur != dev) (void)hipSetDevice(cur);
+    return rc;
+}
+
+int MPIR_Hip_batch_plan_info(const MPIR_Hip_seg *segs, int nsegs, int op, int elem, uint64_t out[6],
+                             uint32_t *seg_kind, uint32_t *seg_groups) {
+    if (!batch_args_ok(segs, nsegs, op, elem)) return MPIR_HIP_ENOKERNEL;
+    const BatchEntry &en = g_batch[op][elem];
+    uint64_t totals[5];
+    const int one = batch_single(segs, nsegs);
+    if (one >= 0) {
+        // the single call's own plan (MPIR_Hip_plan_info)
+        const plan_fn fn = g_table[op][elem].plan ? g_table[op][elem].plan : g_table[op][elem].wide;
+        if (!fn) return MPIR_HIP_ENOKERNEL;
+        ReducePlan p;
+        fn(segs[one].in, segs[one].io, segs[one].count, &p);
+        for (int i = 0; i < nsegs; ++i) {
+            if (seg_kind) seg_kind[i] = i == one ? MPIR_HIP_BATCH_SEG_SINGLE : MPIR_HIP_BATCH_SEG_EMPTY;
+            if (seg_groups) seg_groups[i] = i == one ? (uint32_t)p.groups : 0;
+        }
+        totals[0] = 1;
+        totals[1] = p.groups;
+        totals[2] = totals[3] = 0;
+        totals[4] = (uint64_t)nsegs - 1;
+    } else {
+        batch_launches(en, segs, nsegs, seg_kind, seg_groups, totals, [](const BatchArgs &, uint64_t) { return true; });
+    }
+    for (int k = 0; k < 5; ++k) out[k] = totals[k];
+    out[5] = (uint64_t)kBatchMaxSegs;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_reduce_batch(const MPIR_Hip_seg *segs, int nsegs, int op, int elem, void *hip_stream, int sync) {
+    if (!batch_args_ok(segs, nsegs, op, elem)) return MPIR_HIP_ENOKERNEL;
+    const BatchEntry &en = g_batch[op][elem];
+    ctx().err[0] = 0;
+    // every pointer is classified, and every segment sized, before anything is
+    // launched: a call that fails has written nothing
+    int dev = -1, nonempty = 0;
+    DeviceSpan span_in, span_io;
+    for (int i = 0; i < nsegs; ++i) {
+        if (!segs[i].count) continue;
+        int din = -1, dio = -1, tile = 0;
+        if (classify_in_span(segs[i].in, &din, span_in) != LOC_DEVICE ||
+            classify_in_span(segs[i].io, &dio, span_io) != LOC_DEVICE || din != dio ||
+            (nonempty && dio != dev))
+            return MPIR_HIP_EBUFFER;
+        dev = dio;
+        ++nonempty;
+        if (en.groups(segs[i].in, segs[i].io, segs[i].count, &tile) > kBatchMaxGroups) {
+            snprintf(ctx().err, sizeof(ctx().err), "batch segment %d needs more workgroups than one launch holds", i);
+            return MPIR_HIP_ERUNTIME;
+        }
+    }
+    if (nonempty == 0) return MPIR_HIP_OK;
+    if (nonempty == 1) {
+        // the single call: the direct AQL dispatch when synchronous, every existing plan
+        const MPIR_Hip_seg &s = segs[batch_single(segs, nsegs)];
+        return MPIR_Hip_reduce(s.in, s.io, s.count, op, elem, hip_stream, sync);
+    }
+    int cur = 0;
+    HIPCHK(hipGetDevice(&cur));
+    if (cur != dev) HIPCHK(hipSetDevice(dev));
+    hipStream_t s = (hipStream_t)hip_stream;
+    int rc = MPIR_HIP_OK;
+    if (!s) rc = get_stream(dev, S_MAIN, &s);
+    if (rc == MPIR_HIP_OK) {
+        hipError_t e = hipSuccess;
+        uint64_t totals[5];
+        batch_launches(en, segs, nsegs, nullptr, nullptr, totals, [&](const BatchArgs &a, uint64_t groups) {
+            e = en.launch(&a, groups, s);
+            return e == hipSuccess;
+        });
+        // (launches made before one that failed are still queued on the library stream)
+        if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
+        if (e != hipSuccess) rc = set_err(e, "batch launch");
+        else if (sync) rc = wait_stream(dev, s);
+    }
     if (cur != dev) (void)hipSetDevice(cur);
     return rc;
 }

@@ -31,6 +31,8 @@ typedef hipError_t (*multi_fn)(const void *const *, void *, uint64_t, hipStream_
 typedef void (*host_fn)(const void *, void *, uint64_t);
 typedef void (*plan_fn)(const void *, void *, uint64_t, ReducePlan *);
 typedef void (*split_fn)(const void *const *, int, const void *, uint64_t, CombineSplit *);
+typedef hipError_t (*batch_fn)(const BatchArgs *, uint64_t, hipStream_t);
+typedef uint64_t (*bgroups_fn)(const void *, const void *, uint64_t, int *);
 
 // plan: plan_reduce<T> (reduce_kernels.hpp) for the classes whose launcher is
 // launch_reduce -- the kernel, grid and argument bytes the direct AQL dispatch
@@ -40,6 +42,12 @@ typedef void (*split_fn)(const void *const *, int, const void *, uint64_t, Combi
 // launches); split: combine_split<T> for the pairs with fused folds (what
 // launch_combine_pu launches).  Both are read by the plan introspection only.
 struct Entry { launch_fn fn; any_fn any; host_fn host; plan_fn plan; plan_fn wide; split_fn split; };
+// g_batch[op][elem], a table of its own beside g_table (whose layout stays as
+// it was): launch = launch_batch<Op, T>, one launch of k_reduce_batch over a
+// segment table (MPIR_Hip_reduce_batch), for every pair with fn but REPLACE;
+// groups = batch_groups_any<T>, a segment's path and workgroup count for the
+// batch's planner.
+struct BatchEntry { batch_fn launch; bgroups_fn groups; };
 
 // float / double SUM and PROD on the host: the SSE instruction itself.  The
 // reference's loop `a[i] = a[i] + b[i]` (opsum.c:21-76, gcc -O2) is an
@@ -107,6 +115,7 @@ void host_loop(const void *in, void *io, uint64_t n) {
     }
 }
 extern Entry g_table[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 constexpr int kMultiMaxP = 8;
 extern multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 
@@ -117,6 +126,7 @@ void reg(int op, int elem) {
     if constexpr (!__is_same(Op, OpReplace)) {
         g_table[op][elem].any = &launch_combine_any<Op, T>;
         g_table[op][elem].plan = &plan_reduce_any<T>;
+        g_batch[op][elem] = BatchEntry{&launch_batch<Op, T>, &batch_groups_any<T>};
     }
 }
 template <class Op, class T, int EPL = 2>
@@ -125,6 +135,7 @@ void reg_wide(int op, int elem) {
     g_table[op][elem].wide = &plan_reduce_wide<T, EPL>;
     g_table[op][elem].host = &host_loop<Op, T>;
     g_table[op][elem].any = &launch_combine_any<Op, T>;
+    g_batch[op][elem] = BatchEntry{&launch_batch<Op, T>, &batch_groups_any<T>};
 }
 template <class Op, class T>
 void reg_multi(int op, int elem) {

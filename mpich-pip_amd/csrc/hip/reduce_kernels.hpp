@@ -28,6 +28,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mpir_hip_reduce.h"
 #include "reduce_ops.hpp"
 
 namespace mpir_hip {
@@ -607,6 +608,157 @@ hipError_t launch_reduce_wide(const void *in_, void *io_, uint64_t count, hipStr
     __builtin_memcpy(&a, p.args, sizeof a);
     hipLaunchKernelGGL((k_reduce_elems<Op, T, false>), dim3((unsigned)p.groups), dim3(kThreads), 0, s, a.in, a.io, a.n,
                        a.stride);
+    return hipGetLastError();
+}
+
+// ============================================================================
+// Batched reductions (MPIR_Hip_reduce_batch): many independent (in, io, count)
+// segments under one (op, type) in ONE launch, each segment's result what the
+// single call gives.  A synchronous small call costs what the command
+// processor takes to start and retire a dispatch, whatever its size; a caller
+// with many small combines to make pays that once here.
+//
+//   * The segment table travels by value in the kernel arguments (as AnyArgs'
+//     64 pointers do): no device table, copy or scratch, so an enqueued batch
+//     is self-contained.  kBatchMaxSegs descriptors fit HIP's 4 KiB of kernel
+//     arguments; a larger batch is several back-to-back launches.
+//   * The grid is the sum of the segments' workgroup counts.  A workgroup finds
+//     its segment by a binary search of the descriptors' first workgroups --
+//     uniform across the workgroup, so scalar loads from the kernarg segment --
+//     and takes tile blockIdx.x - first of it.
+//   * A segment whose pointers are naturally aligned and share their offset
+//     mod 16 (seg_split) runs reduce_tile on the 16 KiB grid of inoutbuf's
+//     address, exactly as k_reduce_tile does, its tile 0 also the head and tail
+//     elements; stores are nt (keep = 0: batched segments are small, and the
+//     single call stores results of at most 16 MiB nt too).  Every other
+//     segment, and every segment of the 32-byte classes, runs the element form:
+//     workgroup g of it owns elements [g, g + 1) x kTileBytes / sizeof(T).
+//   * seg_split / batch_seg_groups are the one source of a segment's split and
+//     workgroup count: the host's planner sums the count into the descriptors'
+//     first workgroups and the kernel bounds its tile index by it.
+// ============================================================================
+// The split of one segment, on the pointer values alone: tile_split's
+// condition and arithmetic (head elements to 16 B-align inoutbuf / a 16 B
+// vector body / tail elements), restated as a __host__ __device__ function so
+// that the batch's planner and its kernel, which splits each of its segments on
+// the device, take it from one place.  tests/test_batch_cpu.py holds it to
+// tile_split: a tile-path segment's workgroups are MPIR_Hip_plan_info's.
+struct SegSplit {
+    bool tile;              // the tile kernels apply (false: the counts below are 0)
+    uint64_t head_bytes;    // bytes before the vector region (at most the payload)
+    uint64_t vbytes;        // multiple of 16
+    uint32_t nhead, ntail;  // elements
+};
+template <class T>
+__host__ __device__ inline SegSplit seg_split(const void *in, const void *io, uint64_t count) {
+    SegSplit s = {false, 0, 0, 0, 0};
+    if constexpr (sizeof(T) <= 16) {
+        const uintptr_t ai = reinterpret_cast<uintptr_t>(in), ao = reinterpret_cast<uintptr_t>(io);
+        const uint64_t nbytes = count * sizeof(T);
+        const bool natural = (ai % alignof(T) == 0) && (ao % alignof(T) == 0);
+        const uint64_t head0 = (16 - (ao & 15)) & 15;
+        if (!(natural && ((ai ^ ao) & 15) == 0 && head0 % sizeof(T) == 0)) return s;
+        const uint64_t head_bytes = head0 < nbytes ? head0 : nbytes;
+        const uint64_t rest = nbytes - head_bytes;
+        s.tile = true;
+        s.head_bytes = head_bytes;
+        s.vbytes = rest & ~(uint64_t)15;
+        s.nhead = (uint32_t)(head_bytes / sizeof(T));
+        s.ntail = (uint32_t)((rest - s.vbytes) / sizeof(T));
+    }
+    return s;
+}
+
+// element i of a segment: io[i] = op(io[i], in[i]), the element form of
+// reduce_elems<..., false> (any alignment)
+template <class Op, class T>
+__device__ __forceinline__ void batch_elem_at(const char *in, char *io, uint64_t i) {
+    Op op;
+    T x, y;
+    __builtin_memcpy(&x, io + i * sizeof(T), sizeof(T));
+    __builtin_memcpy(&y, in + i * sizeof(T), sizeof(T));
+    x = op(x, y);
+    __builtin_memcpy(io + i * sizeof(T), &x, sizeof(T));
+}
+
+constexpr int kBatchMaxSegs = 127;
+// a launch closes before its workgroups pass this: 2^23 x 256 threads keeps the
+// grid's work-item count inside the 32 bits an AQL packet holds
+constexpr uint64_t kBatchMaxGroups = MPIR_HIP_BATCH_MAX_GROUPS;
+
+struct BatchSeg {
+    const char *in;
+    char *io;
+    uint64_t count;     // elements, > 0
+    uint64_t first;     // the segment's first workgroup in this launch's grid
+};
+struct BatchArgs {
+    uint32_t nsegs;     // descriptors in use, >= 1; seg[0].first == 0, first strictly increasing
+    uint32_t pad_;
+    BatchSeg seg[kBatchMaxSegs];
+};
+static_assert(sizeof(BatchArgs) <= 4096, "the segment table must fit HIP's 4 KiB of kernel arguments");
+static_assert(kBatchMaxGroups * kThreads < (1ull << 32), "the grid's work-items must fit an AQL packet's 32 bits");
+
+// workgroups of one segment (count > 0), given its split
+template <class T>
+__host__ __device__ inline uint64_t batch_seg_groups(const SegSplit &s, const void *io, uint64_t count) {
+    if (s.tile) return tile_groups(static_cast<const char *>(io) + s.head_bytes, s.vbytes);
+    constexpr uint64_t per = kTileBytes / sizeof(T);
+    return (count + per - 1) / per;
+}
+
+// the same, type-erased (BatchEntry::groups, kernel_table.hpp); *tile: the path
+template <class T>
+uint64_t batch_groups_any(const void *in, const void *io, uint64_t count, int *tile) {
+    const SegSplit s = seg_split<T>(in, io, count);
+    *tile = s.tile;
+    return batch_seg_groups<T>(s, io, count);
+}
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_reduce_batch(BatchArgs a) {
+    const uint32_t wg = blockIdx.x;
+    uint32_t lo = 0, hi = a.nsegs;          // seg[lo].first <= wg < seg[hi].first (hi == nsegs: the grid's end)
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (a.seg[mid].first <= wg) lo = mid;
+        else hi = mid;
+    }
+    const char *in = a.seg[lo].in;
+    char *io = a.seg[lo].io;
+    const uint64_t count = a.seg[lo].count;
+    const uint64_t tile = wg - a.seg[lo].first;
+    const SegSplit s = seg_split<T>(in, io, count);
+    if (tile >= batch_seg_groups<T>(s, io, count)) return;
+    if constexpr (sizeof(T) <= 16) {
+        if (s.tile) {
+            reduce_tile<Op, T>(in + s.head_bytes, io + s.head_bytes, tile, s.vbytes, 0);
+            if (tile == 0) {
+                Op op;
+                const unsigned t = threadIdx.x;
+                if (t < s.nhead) {
+                    T *p = reinterpret_cast<T *>(io) + t;
+                    *p = op(*p, reinterpret_cast<const T *>(in)[t]);
+                } else if (t >= 64 && t - 64 < s.ntail) {
+                    T *p = reinterpret_cast<T *>(io + s.head_bytes + s.vbytes) + (t - 64);
+                    *p = op(*p, reinterpret_cast<const T *>(in + s.head_bytes + s.vbytes)[t - 64]);
+                }
+            }
+            return;
+        }
+    }
+    constexpr uint64_t per = kTileBytes / sizeof(T);
+    const uint64_t base = tile * per;
+    const uint64_t end = base + per < count ? base + per : count;
+    for (uint64_t i = base + threadIdx.x; i < end; i += kThreads) batch_elem_at<Op, T>(in, io, i);
+}
+
+template <class Op, class T>
+hipError_t launch_batch(const BatchArgs *a, uint64_t groups, hipStream_t s) {
+    if (a->nsegs < 1 || a->nsegs > (uint32_t)kBatchMaxSegs || groups < 1 || groups > kBatchMaxGroups)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_reduce_batch<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
     return hipGetLastError();
 }
 

@@ -401,6 +401,90 @@ static int reduce_local_multi(const void *const *inbufs, int n, void *outbuf, in
     return MPI_SUCCESS;
 }
 
+/* ---- MPIX_Reduce_local_batch: many segments, one launch (see the header) */
+/* The shim's batch entry is bound weakly, so that a program which links this
+ * file against a partial shim of its own (a harness that stubs only the
+ * MPIR_Hip_* entries its collectives reach) still links; without the entry the
+ * call fails with MPI_ERR_OTHER. */
+#pragma weak MPIR_Hip_reduce_batch
+static int reduce_local_batch(const MPIX_Reduce_local_seg * segs, int nsegs, MPI_Datatype datatype,
+                              MPI_Op op, void *hip_stream);
+
+int MPIX_Reduce_local_batch(const MPIX_Reduce_local_seg * segs, int nsegs, MPI_Datatype datatype,
+                            MPI_Op op, void *hip_stream)
+{
+    int rc;
+    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
+    rc = reduce_local_batch(segs, nsegs, datatype, op, hip_stream);
+    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
+    return rc;
+}
+
+static int reduce_local_batch(const MPIX_Reduce_local_seg * segs, int nsegs, MPI_Datatype datatype,
+                              MPI_Op op, void *hip_stream)
+{
+    static const char *fc = "MPIX_Reduce_local_batch";
+    MPIR_Hip_seg small[64], *hs = small;
+    int mpi_errno, opidx, elem, rc, j, nonempty = 0;
+    if (nsegs < 0 || (nsegs > 0 && !segs)) {
+        MPIR_Err_set_detail("invalid segment count or segment array");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    /* everything is validated before anything is launched */
+    for (j = 0; j < nsegs; j++) {
+        if (segs[j].count < 0) {
+            MPIR_Err_set_detail("segment %d: negative count %d", j, segs[j].count);
+            return err_return(fc, MPI_ERR_COUNT);
+        }
+        /* an empty segment's pointers are not looked at (the op still is) */
+        mpi_errno = segs[j].count ? validate(segs[j].inbuf, segs[j].inoutbuf, segs[j].count, datatype, op)
+            : validate(NULL, NULL, 0, datatype, op);
+        if (mpi_errno != MPI_SUCCESS)
+            return err_return(fc, mpi_errno);
+        nonempty += segs[j].count != 0;
+    }
+    if (!nonempty)
+        return MPI_SUCCESS;
+    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
+        MPIR_Err_set_detail("user MPI_Op functions run on the host; use MPI_Reduce_local");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    opidx = op & 0xf;
+    elem = MPIR_Op_resolve_elem(opidx, datatype);
+    if (!elem) {        /* compute switch `default:` (LAND/LOR on floats) */
+        MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    if (!MPIR_Hip_reduce_batch) {
+        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_batch");
+        return err_return(fc, MPI_ERR_OTHER);
+    }
+    if (nsegs > (int) (sizeof small / sizeof small[0])) {
+        hs = (MPIR_Hip_seg *) malloc((size_t) nsegs * sizeof *hs);
+        if (!hs) {
+            MPIR_Err_set_detail("out of memory for %d segments", nsegs);
+            return err_return(fc, MPI_ERR_NO_MEM);
+        }
+    }
+    for (j = 0; j < nsegs; j++) {
+        hs[j].in = segs[j].inbuf;
+        hs[j].io = segs[j].inoutbuf;
+        hs[j].count = (uint64_t) segs[j].count;
+    }
+    rc = MPIR_Hip_reduce_batch(hs, nsegs, opidx, elem, hip_stream, hip_stream == NULL);
+    if (hs != small)
+        free(hs);
+    if (rc == MPIR_HIP_EBUFFER) {
+        MPIR_Err_set_detail("%s needs device-resident buffers on one device", fc);
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (rc != MPIR_HIP_OK) {
+        MPIR_Op_report_hip_error(fc, rc);
+        return err_return(fc, *MPIR_Op_errno_ptr());
+    }
+    return MPI_SUCCESS;
+}
+
 /* ---- MPI_Op_create / MPI_Op_free / MPI_Op_commutative ------------------ */
 int PMPI_Op_create(MPI_User_function * user_fn, int commute, MPI_Op * op)
 {

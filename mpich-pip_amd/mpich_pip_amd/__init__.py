@@ -111,6 +111,7 @@ EXPORTED_SYMBOLS = [
     "MPI_Error_class", "MPI_Error_string",
     "MPIX_Reduce_local_stream", "MPIX_Reduce_local_set_errhandler", "MPIX_Reduce_local_get_errhandler",
     "MPIX_Reduce_local_multi", "MPIR_Hip_combine",
+    "MPIX_Reduce_local_batch", "MPIR_Hip_reduce_batch", "MPIR_Hip_batch_plan_info",
     # device collectives (include/mpix_hip_coll.h)
     "MPIX_Hip_comm_get_unique_id", "MPIX_Hip_comm_create", "MPIX_Hip_comm_create_loopback",
     "MPIX_Hip_comm_free", "MPIX_Hip_comm_rank", "MPIX_Hip_comm_size",
@@ -133,6 +134,18 @@ EXPORTED_SYMBOLS = [
 
 MPI_User_function = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int))
+
+
+
+class ReduceLocalSeg(ctypes.Structure):
+    """MPIX_Reduce_local_seg (include/mpi_reduce_local.h)."""
+    _fields_ = [("inbuf", ctypes.c_void_p), ("inoutbuf", ctypes.c_void_p), ("count", ctypes.c_int)]
+
+
+class HipSeg(ctypes.Structure):
+    """MPIR_Hip_seg (include/mpir_hip_reduce.h)."""
+    _fields_ = [("inbuf", ctypes.c_void_p), ("inoutbuf", ctypes.c_void_p), ("count", ctypes.c_uint64)]
+
 
 _lib = None
 
@@ -161,6 +174,13 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.MPIX_Reduce_local_stream.restype = i32
     lib.MPIX_Reduce_local_multi.argtypes = [ctypes.POINTER(vp), i32, vp, i32, i32, i32, i32, vp]
     lib.MPIX_Reduce_local_multi.restype = i32
+    lib.MPIX_Reduce_local_batch.argtypes = [ctypes.POINTER(ReduceLocalSeg), i32, i32, i32, vp]
+    lib.MPIX_Reduce_local_batch.restype = i32
+    lib.MPIR_Hip_reduce_batch.argtypes = [ctypes.POINTER(HipSeg), i32, i32, i32, vp, i32]
+    lib.MPIR_Hip_reduce_batch.restype = i32
+    lib.MPIR_Hip_batch_plan_info.argtypes = [ctypes.POINTER(HipSeg), i32, i32, i32, ctypes.POINTER(ctypes.c_uint64),
+                                             ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
+    lib.MPIR_Hip_batch_plan_info.restype = i32
     lib.MPIX_Hip_comm_get_unique_id.argtypes = [vp]
     lib.MPIX_Hip_comm_get_unique_id.restype = i32
     lib.MPIX_Hip_comm_create.argtypes = [vp, i32, i32, ctypes.POINTER(vp)]
@@ -375,6 +395,41 @@ def combine_plan_info(inbufs, outbuf: int, count: int, datatype: int, op: int, o
     if rc:
         raise LookupError(f"MPIR_Hip_combine_plan_info: {rc}")
     return dict(zip(("path", "passes", "nhead", "ntail"), (int(v) for v in out)))
+
+
+# ---- batched reductions (MPIX_Reduce_local_batch)
+BATCH_SEG_EMPTY, BATCH_SEG_TILE, BATCH_SEG_ELEMS, BATCH_SEG_SINGLE = range(4)
+BATCH_SEG_NAMES = ["empty", "tile", "elems", "single"]
+BATCH_MAX_GROUPS = 1 << 23      # MPIR_HIP_BATCH_MAX_GROUPS: a launch closes before its workgroups pass it
+
+
+def reduce_local_batch(segs, datatype: int, op: int, stream: int = 0) -> int:
+    """MPIX_Reduce_local_batch: `segs` is an iterable of (inbuf, inoutbuf, count)
+    on raw device addresses; one launch combines them all.  stream 0: synchronous
+    on the library stream; otherwise enqueued on that HIP stream, no wait."""
+    segs = list(segs)
+    arr = (ReduceLocalSeg * max(len(segs), 1))(*[ReduceLocalSeg(i or None, o or None, n) for i, o, n in segs])
+    return load().MPIX_Reduce_local_batch(arr, len(segs), datatype, op, ctypes.c_void_p(stream or None))
+
+
+def batch_plan_info(segs, datatype: int, op: int) -> dict:
+    """MPIR_Hip_batch_plan_info: the launches of a batch of device segments at
+    these addresses (never dereferenced; no GPU needed): launches, groups (over
+    all launches), tile / elems / empty (segments per path), max_segs (per
+    launch), and per segment seg_kind (BATCH_SEG_*) and seg_groups.  Raises where
+    the pair has no batch kernel."""
+    segs = list(segs)
+    n = len(segs)
+    arr = (HipSeg * max(n, 1))(*[HipSeg(i or None, o or None, c) for i, o, c in segs])
+    out = (ctypes.c_uint64 * 6)()
+    kind, groups = (ctypes.c_uint32 * max(n, 1))(), (ctypes.c_uint32 * max(n, 1))()
+    rc = load().MPIR_Hip_batch_plan_info(arr, n, op & 0xFF, _ELEM_BY_HANDLE[datatype], out, kind, groups)
+    if rc:
+        raise LookupError(f"MPIR_Hip_batch_plan_info: {rc}")
+    d = dict(zip(("launches", "groups", "tile", "elems", "empty", "max_segs"), (int(v) for v in out)))
+    d["seg_kind"] = [int(kind[i]) for i in range(n)]
+    d["seg_groups"] = [int(groups[i]) for i in range(n)]
+    return d
 
 
 MPIX_HIP_ALG_AUTO = 0
