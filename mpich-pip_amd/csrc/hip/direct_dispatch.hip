@@ -69,6 +69,7 @@
 
 #include "mpir_hip_reduce.h"
 #include "kernel_table.hpp"
+#include "host_env.hpp"      // parse_cpulist
 
 namespace mpir_hip {
 
@@ -835,22 +836,12 @@ static void maybe_bind_near(int dev) {
     if (node < 0) return;
     char path[96];
     snprintf(path, sizeof path, "/sys/devices/system/node/node%d/cpulist", node);
-    FILE *f = fopen(path, "r");
-    if (!f) return;
+    std::vector<int> cpus;
+    if (parse_cpulist(path, cpus) != 0) return;
     cpu_set_t want, have;
     CPU_ZERO(&want);
-    char buf[4096];
-    if (fgets(buf, sizeof buf, f)) {
-        for (char *t = strtok(buf, ",\n"); t; t = strtok(nullptr, ",\n")) {
-            int a = -1, b = -1;
-            if (sscanf(t, "%d-%d", &a, &b) == 2) {
-                for (int c = a; c <= b && c < CPU_SETSIZE; ++c) CPU_SET(c, &want);
-            } else if (sscanf(t, "%d", &a) == 1 && a >= 0 && a < CPU_SETSIZE) {
-                CPU_SET(a, &want);
-            }
-        }
-    }
-    fclose(f);
+    for (int c : cpus)
+        if (c >= 0) CPU_SET(c, &want);
     if (pthread_getaffinity_np(pthread_self(), sizeof have, &have) != 0) return;
     CPU_AND(&want, &want, &have);
     if (CPU_COUNT(&want) > 0) (void)pthread_setaffinity_np(pthread_self(), sizeof want, &want);

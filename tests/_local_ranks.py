@@ -72,7 +72,7 @@ def _cpulist(path: str) -> int:
 
 def job_cpus() -> int:
     """The CPUs the job's ranks share, as the library counts them
-    (hip_reduce.hip online_cpus): the cgroup's cpuset, else the online CPUs."""
+    (host_env.hip online_cpus): the cgroup's cpuset, else the online CPUs."""
     for path in ("/sys/fs/cgroup/cpuset.cpus.effective", "/sys/fs/cgroup/cpuset/cpuset.effective_cpus"):
         n = _cpulist(path)
         if n:

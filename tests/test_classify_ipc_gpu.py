@@ -1,7 +1,7 @@
 """A device buffer imported from another process (hipIpcOpenMemHandle) as an
 MPI_Reduce_local operand: MPICH's intra-node GPU path hands such IPC mappings
 to the reduction.  HSA reports them as IPC memory (hsa_ext_amd.h:2364); the
-library's classify() (hip_reduce.hip) must see a device buffer on the right
+library's classify() (classify.hip) must see a device buffer on the right
 device and combine in place.  The parent allocates and fills the buffer and
 exports its handle; a child process opens it, reduces into it (and from it),
 and the parent checks the bytes against the oracle.  Both sides allocate through

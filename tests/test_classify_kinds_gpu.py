@@ -1,5 +1,5 @@
 """Every kind of buffer a caller can hand MPI_Reduce_local, classified by the
-HSA pointer query (hip_reduce.hip classify) and reduced
+HSA pointer query (classify.hip classify) and reduced
 bit-exact against the oracle.  The reference runs no query at all: its loop
 reads host memory (reduce_local.c:35-122, opsum.c:21-76).
 
@@ -246,7 +246,7 @@ def test_registration_after_kept_verdict(mpi, orc, hip):
     then registered with hipHostRegister -- which HSA still reports as UNKNOWN --
     and reduced large: the large call asks HIP again and sees it pinned; after
     hipHostUnregister a large call sees it pageable again.  Every reduction
-    bit-exact (hip_reduce.hip classify, `reuse`)."""
+    bit-exact (classify.hip classify, `reuse`)."""
     lib = mpi.load()
     err = []
 
@@ -307,7 +307,7 @@ def test_kept_pageable_verdict_orders_after_null_stream(mpi, orc, hip):
     by a null-stream hipMemcpyAsync queued behind a 512 MiB device copy, and a
     small host-host MPI_Reduce_local(C, B) follows at once.  B's page answers
     with A's kept pageable verdict; the call must still wait for the null
-    stream before reading B (hip_reduce.hip classify `kept`), so B ends as
+    stream before reading B (classify.hip classify `kept`), so B ends as
     copied + C, bit-exact against the oracle."""
     lib = mpi.load()
     err = []

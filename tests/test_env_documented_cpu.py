@@ -38,8 +38,8 @@ def test_every_variable_is_documented():
 
 def test_local_rank_variables_documented():
     """The launchers' node-local rank counts the host pool reads (round 5;
-    hip_reduce.hip local_ranks reads them in a loop the scan above cannot see)."""
-    with open(os.path.join(ROOT, "mpich-pip_amd", "csrc", "hip", "hip_reduce.hip"), encoding="utf-8") as fh:
+    host_env.hip local_ranks reads them in a loop the scan above cannot see)."""
+    with open(os.path.join(ROOT, "mpich-pip_amd", "csrc", "hip", "host_env.hip"), encoding="utf-8") as fh:
         src = fh.read()
     with open(os.path.join(ROOT, "INTEGRATION.md"), encoding="utf-8") as fh:
         doc = fh.read()

@@ -6,7 +6,7 @@ and Hydra's MPI_LOCALNRANKS, pmip_cb.c:658-662).
 64 MiB fp32 SUM MPI_Reduce_local on host buffers at the same moment (a barrier
 on a pipe, tests/_local_ranks.py): together they run no more threads than the
 CPUs the job may use, and every result is bit-exact against the oracle.  The
-sizing rule itself (hip_reduce.hip share_threads) is checked through single
+sizing rule itself (host_env.hip share_threads) is checked through single
 processes under chosen masks and rank counts.
 """
 import os
