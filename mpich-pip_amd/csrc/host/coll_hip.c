@@ -31,6 +31,12 @@
 #define COMM_RCCL 1
 #define COMM_LOOPBACK 2
 #define MAX_XFER 256
+/* Ranks of a communicator: the loopback hub's slots and every per-rank array
+ * (cnts / disps / ys / chain).  A combine takes one operand per rank, so this
+ * is also MPIR_Hip_combine's operand limit (kMaxAnyOperands = 64 in
+ * csrc/hip/reduce_kernels.hpp; mpir_hip_reduce.h documents "n <= 64" but
+ * exposes no constant to check against: keep the two equal by hand). */
+#define MAX_RANKS 64
 #define REDUCE_SHORT_MSG_SIZE 2048            /* reduce.c:14-17 */
 #define RSB_COMMUTATIVE_LONG_MSG_SIZE 524288  /* reduce_scatter.c:14-17 */
 
@@ -113,8 +119,10 @@ typedef struct loop_hub {
         int nsend;
         xfer_t sends[MAX_XFER];
         hipEvent_t ready;
-    } slot[64];
+    } slot[MAX_RANKS];
 } loop_hub_t;
+_Static_assert(sizeof(((loop_hub_t *) 0)->slot) / sizeof(((loop_hub_t *) 0)->slot[0]) == MAX_RANKS,
+               "one hub slot per rank of the largest communicator");
 
 #define MAX_PIPE 16            /* chunks of a pipelined exchange (pipe_chunks) */
 
@@ -131,11 +139,36 @@ struct MPIX_Hip_comm_s {
     hipEvent_t xev[MAX_PIPE], fev[MAX_PIPE];
 };
 
-static int hip_fail(const char *fc, hipError_t e)
+/* One call of a collective: what coll_begin() settles for every one of them
+ * and coll_end() undoes. */
+typedef struct {
+    const char *fc;             /* the MPIX_ entry point, for error reports */
+    struct MPIX_Hip_comm_s *c;
+    hipStream_t s;
+    int user_stream;            /* s is the caller's: left unsynchronised */
+    int saved_device, switched; /* the caller's device, and whether it was left */
+    int elem, opidx;
+    size_t esz;
+} coll_t;
+
+/* ------------------------------------------------------------ error reports:
+ * each sets the detail and returns the MPI error class; the entry points turn
+ * it into the final code (MPIR_Err_return) */
+static int hip_err(const char *fc, hipError_t e)
 {
     MPIR_Err_set_detail("%s: HIP error %s", fc, hipGetErrorString(e));
-    return MPIR_Err_return(fc, MPI_ERR_OTHER);
+    return MPI_ERR_OTHER;
 }
+
+static int rccl_err(const char *what, ncclResult_t r)
+{
+    MPIR_Err_set_detail("%s: %s", what, rccl.GetErrorString ? rccl.GetErrorString(r) : "?");
+    return MPI_ERR_OTHER;
+}
+
+#define HIPTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
+        MPIR_Err_set_detail("%s: %s", #x, hipGetErrorString(e_)); return MPI_ERR_OTHER; } } while (0)
+#define TRY(x) do { int rc_ = (x); if (rc_ != MPI_SUCCESS) return rc_; } while (0)
 
 static int comm_init_common(struct MPIX_Hip_comm_s *c)
 {
@@ -154,10 +187,8 @@ int MPIX_Hip_comm_get_unique_id(void *id)
         return MPIR_Err_return("MPIX_Hip_comm_get_unique_id", MPI_ERR_OTHER);
     }
     r = rccl.GetUniqueId(&u);
-    if (r != ncclSuccess) {
-        MPIR_Err_set_detail("ncclGetUniqueId: %s", rccl.GetErrorString ? rccl.GetErrorString(r) : "?");
-        return MPIR_Err_return("MPIX_Hip_comm_get_unique_id", MPI_ERR_OTHER);
-    }
+    if (r != ncclSuccess)
+        return MPIR_Err_return("MPIX_Hip_comm_get_unique_id", rccl_err("ncclGetUniqueId", r));
     memcpy(id, &u, sizeof(u));
     return MPI_SUCCESS;
 }
@@ -169,7 +200,7 @@ int MPIX_Hip_comm_create(const void *id, int size, int rank, MPIX_Hip_comm * com
     ncclUniqueId u;
     ncclResult_t r;
     int e;
-    if (size < 1 || rank < 0 || rank >= size || size > 64) {
+    if (size < 1 || rank < 0 || rank >= size || size > MAX_RANKS) {
         MPIR_Err_set_detail("%s: invalid size/rank", fc);
         return MPIR_Err_return(fc, MPI_ERR_ARG);
     }
@@ -183,15 +214,14 @@ int MPIX_Hip_comm_create(const void *id, int size, int rank, MPIX_Hip_comm * com
     c->size = size;
     if ((e = comm_init_common(c)) != 0) {
         free(c);
-        return hip_fail(fc, (hipError_t) e);
+        return MPIR_Err_return(fc, hip_err(fc, (hipError_t) e));
     }
     memcpy(&u, id, sizeof(u));
     r = rccl.CommInitRank(&c->nccl, size, u, rank);
     if (r != ncclSuccess) {
-        MPIR_Err_set_detail("ncclCommInitRank: %s", rccl.GetErrorString ? rccl.GetErrorString(r) : "?");
         (void) hipStreamDestroy(c->stream);
         free(c);
-        return MPIR_Err_return(fc, MPI_ERR_OTHER);
+        return MPIR_Err_return(fc, rccl_err("ncclCommInitRank", r));
     }
     *comm = c;
     return MPI_SUCCESS;
@@ -202,8 +232,8 @@ int MPIX_Hip_comm_create_loopback(int size, MPIX_Hip_comm * comms)
     static const char *fc = "MPIX_Hip_comm_create_loopback";
     loop_hub_t *hub;
     int r, e;
-    if (size < 1 || size > 64) {
-        MPIR_Err_set_detail("%s: size must be 1..64", fc);
+    if (size < 1 || size > MAX_RANKS) {
+        MPIR_Err_set_detail("%s: size must be 1..%d", fc, MAX_RANKS);
         return MPIR_Err_return(fc, MPI_ERR_ARG);
     }
     hub = calloc(1, sizeof(*hub));
@@ -218,9 +248,9 @@ int MPIX_Hip_comm_create_loopback(int size, MPIX_Hip_comm * comms)
         c->size = size;
         c->hub = hub;
         if ((e = comm_init_common(c)) != 0)
-            return hip_fail(fc, (hipError_t) e);
+            return MPIR_Err_return(fc, hip_err(fc, (hipError_t) e));
         if ((e = hipEventCreateWithFlags(&hub->slot[r].ready, hipEventDisableTiming)) != hipSuccess)
-            return hip_fail(fc, (hipError_t) e);
+            return MPIR_Err_return(fc, hip_err(fc, (hipError_t) e));
         comms[r] = c;
     }
     return MPI_SUCCESS;
@@ -278,7 +308,8 @@ int MPIX_Hip_comm_size(MPIX_Hip_comm comm, int *size)
     return MPI_SUCCESS;
 }
 
-static int comm_scratch(struct MPIX_Hip_comm_s *c, size_t bytes, char **out)
+/* the communicator's scratch, grown to `bytes` */
+static int comm_scratch(struct MPIX_Hip_comm_s *c, size_t bytes, char **out, const char *fc)
 {
     if (c->scratch_bytes < bytes) {
         hipError_t e;
@@ -290,12 +321,14 @@ static int comm_scratch(struct MPIX_Hip_comm_s *c, size_t bytes, char **out)
         c->scratch = NULL;
         c->scratch_bytes = 0;
         e = hipMalloc(&c->scratch, bytes);
-        if (e != hipSuccess)
-            return (int) e;
+        if (e != hipSuccess) {
+            MPIR_Err_set_detail("%s: scratch allocation failed", fc);
+            return MPI_ERR_NO_MEM;
+        }
         c->scratch_bytes = bytes;
     }
     *out = c->scratch;
-    return 0;
+    return MPI_SUCCESS;
 }
 
 /* ------------------------------------------------------------ transport:
@@ -318,11 +351,7 @@ static int group_exchange(struct MPIX_Hip_comm_s *c, const xfer_t *sends, int ns
             if (r == ncclSuccess)
                 r = r2;
         }
-        if (r != ncclSuccess) {
-            MPIR_Err_set_detail("RCCL grouped send/recv: %s", rccl.GetErrorString ? rccl.GetErrorString(r) : "?");
-            return MPI_ERR_OTHER;
-        }
-        return MPI_SUCCESS;
+        return r == ncclSuccess ? MPI_SUCCESS : rccl_err("RCCL grouped send/recv", r);
     } else {
         /* loopback: post sends + a ready event; every receiver copies from the
          * matching sender once that event has fired; barrier both sides so no
@@ -437,31 +466,82 @@ static void chunk_of(const xfer_t *x, int n, int k, size_t chunk, xfer_t *out)
     }
 }
 
-/* The fold of one chunk: `len` bytes at byte offset `off` of the schedule's
- * output, on stream fs. */
-typedef int (*chunk_fold_fn)(void *ctx, size_t off, size_t len, hipStream_t fs);
+/* ------------------------------------------------------------ folds
+ * the two kernels every schedule is built from, with their error report */
+static int kernel_err(const coll_t *f, int rc)
+{
+    if (rc) {
+        MPIR_Op_report_hip_error(f->fc, rc);
+        return MPI_ERR_OTHER;
+    }
+    return MPI_SUCCESS;
+}
 
-/* Exchange `sends` / `recvs` in nchunk groups on s; after group k, fold(k)
- * on the fold stream, ordered after it by xev[k]; fev[k] marks fold k done.
- * `out_bytes` is the fold's output length (its chunks are [k * chunk, ...)). */
-static int exchange_fold_pipelined(struct MPIX_Hip_comm_s *c, const xfer_t *sends, int nsend, const xfer_t *recvs,
-                                   int nrecv, int nchunk, size_t chunk, size_t out_bytes, hipStream_t s,
-                                   chunk_fold_fn fold, void *ctx)
+static int fold_combine(const coll_t *f, const void *const *ys, int n, void *out, long count, int order,
+                        hipStream_t s)
+{
+    return kernel_err(f, MPIR_Hip_combine(ys, n, out, (uint64_t) count, f->opidx, f->elem, order, s, 0));
+}
+
+static int fold_tree(const coll_t *f, const void *const *ys, int n, void *out, long count)
+{
+    return fold_combine(f, ys, n, out, count, MPIR_HIP_ORDER_TREE, f->s);
+}
+
+static int fold_step(const coll_t *f, const void *src, void *dst, long count)
+{
+    return kernel_err(f, MPIR_Hip_reduce(src, dst, (uint64_t) count, f->opidx, f->elem, f->s, 0));
+}
+
+/* A pipelined fold: `out_bytes` of output from n operands, folded chunk by
+ * chunk with operands and output shifted by the chunk's offset. */
+typedef struct {
+    const void *const *ys;
+    int n, order;
+    char *out;
+    size_t out_bytes;
+} fold_ctx_t;
+
+static int chunk_fold(const coll_t *f, const fold_ctx_t *fo, size_t off, size_t len, hipStream_t fs)
+{
+    const void *ys[MAX_RANKS];
+    int i;
+    for (i = 0; i < fo->n; i++)
+        ys[i] = (const char *) fo->ys[i] + off;
+    return fold_combine(f, ys, fo->n, fo->out + off, (long) (len / f->esz), fo->order, fs);
+}
+
+/* chunk k of `sends` / `recvs` as one group on s */
+static int exchange_chunk(struct MPIX_Hip_comm_s *c, const xfer_t *sends, int nsend, const xfer_t *recvs, int nrecv,
+                          int k, size_t chunk, hipStream_t s)
 {
     xfer_t sk[MAX_XFER], rk[MAX_XFER];
+    chunk_of(sends, nsend, k, chunk, sk);
+    chunk_of(recvs, nrecv, k, chunk, rk);
+    return group_exchange(c, sk, nsend, rk, nrecv, s);
+}
+
+/* Exchange `sends` / `recvs` in nchunk groups on the call's stream; after
+ * group k, chunk k of `fo` (out_bytes 0: this rank folds nothing) on the fold
+ * stream, ordered after it by xev[k]; fev[k] marks fold k done. */
+static int exchange_fold_pipelined(const coll_t *f, const xfer_t *sends, int nsend, const xfer_t *recvs, int nrecv,
+                                   int nchunk, size_t chunk, const fold_ctx_t *fo)
+{
+    struct MPIX_Hip_comm_s *c = f->c;
+    const size_t out_bytes = fo->out_bytes;
+    hipStream_t s = f->s;
     int k, rc = MPI_SUCCESS;
     hipError_t e = hipSuccess;
     for (k = 0; k < nchunk && rc == MPI_SUCCESS; k++) {
         size_t off = (size_t) k * chunk;
-        chunk_of(sends, nsend, k, chunk, sk);
-        chunk_of(recvs, nrecv, k, chunk, rk);
-        if ((rc = group_exchange(c, sk, nsend, rk, nrecv, s)) != MPI_SUCCESS)
+        if ((rc = exchange_chunk(c, sends, nsend, recvs, nrecv, k, chunk, s)) != MPI_SUCCESS)
             break;
         if ((e = hipEventRecord(c->xev[k], s)) != hipSuccess ||
             (e = hipStreamWaitEvent(c->fold_stream, c->xev[k], 0)) != hipSuccess)
             break;
         if (off < out_bytes &&
-            (rc = fold(ctx, off, out_bytes - off < chunk ? out_bytes - off : chunk, c->fold_stream)) != MPI_SUCCESS)
+            (rc = chunk_fold(f, fo, off, out_bytes - off < chunk ? out_bytes - off : chunk,
+                             c->fold_stream)) != MPI_SUCCESS)
             break;
         if ((e = hipEventRecord(c->fev[k], c->fold_stream)) != hipSuccess)
             break;
@@ -473,7 +553,27 @@ static int exchange_fold_pipelined(struct MPIX_Hip_comm_s *c, const xfer_t *send
     return rc;
 }
 
+/* The exchange that follows a pipelined fold, in the same chunks: chunk k
+ * leaves once its fold is done (fev[k]). */
+static int exchange_after_folds(const coll_t *f, const xfer_t *sends, int nsend, const xfer_t *recvs, int nrecv,
+                                int nchunk, size_t chunk)
+{
+    int k;
+    for (k = 0; k < nchunk; k++) {
+        HIPTRY(hipStreamWaitEvent(f->s, f->c->fev[k], 0));
+        TRY(exchange_chunk(f->c, sends, nsend, recvs, nrecv, k, chunk, f->s));
+    }
+    return MPI_SUCCESS;
+}
+
 /* ------------------------------------------------------------ helpers */
+static void xfer_add(xfer_t *list, int *n, const void *buf, size_t bytes, int peer)
+{
+    list[*n].buf = (void *) buf;
+    list[*n].bytes = bytes;
+    list[(*n)++].peer = peer;
+}
+
 /* Byte stride between staging slots.  Slots at a power-of-two stride (equal
  * blocks of a power-of-two message) put the P operand streams of a fused
  * combine on the same HBM channels at the same moment: 8 x 32 MiB TREE8 fp32
@@ -502,6 +602,14 @@ static int pof2_of(int p)
     return q;
 }
 
+static int ilog2(int pof2)
+{
+    int bits = 0;
+    while ((1 << bits) < pof2)
+        bits++;
+    return bits;
+}
+
 static int bitrev(int n, int bits)
 {
     int r = 0, i;
@@ -509,16 +617,6 @@ static int bitrev(int n, int bits)
         if (n & (1 << i))
             r |= 1 << (bits - 1 - i);
     return r;
-}
-
-static void cnts_disps(long count, int pof2, long *cnts, long *disps)
-{
-    int i;
-    for (i = 0; i < pof2; i++)
-        cnts[i] = count / pof2 + (i < count % pof2 ? 1 : 0);
-    disps[0] = 0;
-    for (i = 1; i < pof2; i++)
-        disps[i] = disps[i - 1] + cnts[i - 1];
 }
 
 /* MPIR_Allreduce_intra_auto's branch (allreduce.c:145-217) from the CVARs a
@@ -543,6 +641,13 @@ static int allreduce_flat_choice(size_t bytes, long count, int pof2)
     return FLAT_RABENSEIFNER;
 }
 
+/* The pre-fold of a non-power-of-two communicator pairs the ranks below 2*rem:
+ * pair m = (2m, 2m+1) continues as newrank m, every rank r >= 2*rem as r - rem. */
+static int newrank_of(int rank, int rem)
+{
+    return rank < 2 * rem ? rank / 2 : rank - rem;
+}
+
 /* real rank of newrank m after the pre-fold: the keeper of pair m is the even
  * rank 2m (reduce_intra_reduce_scatter_gather.c) or the odd rank 2m+1
  * (allreduce_intra_reduce_scatter_allgather.c, allreduce_intra_recursive_doubling.c) */
@@ -557,80 +662,63 @@ static int real_of(int m, int rem, int odd_keeps)
  * exchange brings a rank every operand it needs, then the schedule's fold runs
  * on the device (tests/test_schedule_small_cpu.py pins the fold plans against
  * step-by-step simulations of the reference). */
-static int hip_err(const char *fc, hipError_t e)
-{
-    MPIR_Err_set_detail("%s: HIP error %s", fc, hipGetErrorString(e));
-    return MPI_ERR_OTHER;
-}
 
-static int fold_tree(const void *const *ys, int n, void *out, long count, int opidx, int elem, hipStream_t s,
-                     const char *fc)
+/* This rank's vector `x` into slot `rank` of p staging slots, then an
+ * allgather: slot q holds x_q on every rank. */
+static int allgather_slots(const coll_t *f, const void *x, size_t bytes, char **scr)
 {
-    int rc = MPIR_Hip_combine(ys, n, out, (uint64_t) count, opidx, elem, MPIR_HIP_ORDER_TREE, s, 0);
-    if (rc) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return MPI_ERR_OTHER;
-    }
-    return MPI_SUCCESS;
-}
-
-static int fold_step(const void *src, void *dst, long count, int opidx, int elem, hipStream_t s, const char *fc)
-{
-    int rc = MPIR_Hip_reduce(src, dst, (uint64_t) count, opidx, elem, s, 0);
-    if (rc) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return MPI_ERR_OTHER;
-    }
-    return MPI_SUCCESS;
-}
-
-/* MPI_Allreduce, count*size <= 2048 or count < pof2: MPIR_Reduce takes the
- * binomial tree to root 0 (reduce.c:214-225, reduce_intra_binomial.c:93-140:
- * relrank r folds in the accumulation of r|mask as the second operand), then
- * MPIR_Bcast.  Here: an allgather of the p inputs into slots 0..p-1, then every
- * rank folds them in the binomial order itself, so all ranks hold root 0's bytes. */
-static int allreduce_short(struct MPIX_Hip_comm_s *c, const void *sendbuf, void *recvbuf, long count,
-                           size_t esz, int opidx, int elem, hipStream_t s, const char *fc)
-{
-    int p = c->size, q, nx = 0, rc = MPI_SUCCESS, mask;
-    size_t bytes = (size_t) count * esz, slot = stage_stride(bytes);
+    struct MPIX_Hip_comm_s *c = f->c;
+    int p = c->size, q, nsend = 0, nrecv = 0;
+    size_t slot = stage_stride(bytes);
     xfer_t sends[MAX_XFER], recvs[MAX_XFER];
-    const void *ys[64];
-    char *scr = NULL, *own;
+    char *own;
     hipError_t e;
-    if (comm_scratch(c, (size_t) p * slot, &scr)) {
-        MPIR_Err_set_detail("%s: scratch allocation failed", fc);
-        return MPI_ERR_NO_MEM;
-    }
-    own = scr + (size_t) c->rank * slot;
-    e = hipMemcpyAsync(own, sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf, bytes, hipMemcpyDeviceToDevice, s);
+    TRY(comm_scratch(c, (size_t) p * slot, scr, f->fc));
+    own = *scr + (size_t) c->rank * slot;
+    e = hipMemcpyAsync(own, x, bytes, hipMemcpyDeviceToDevice, f->s);
     if (e != hipSuccess)
-        return hip_err(fc, e);
+        return hip_err(f->fc, e);
     for (q = 0; q < p; q++) {
         if (q == c->rank)
             continue;
-        sends[nx].buf = own;
-        sends[nx].bytes = bytes;
-        sends[nx].peer = q;
-        recvs[nx].buf = scr + (size_t) q * slot;
-        recvs[nx].bytes = bytes;
-        recvs[nx++].peer = q;
+        xfer_add(sends, &nsend, own, bytes, q);
+        xfer_add(recvs, &nrecv, *scr + (size_t) q * slot, bytes, q);
     }
-    if ((rc = group_exchange(c, sends, nx, recvs, nx, s)) != MPI_SUCCESS)
-        return rc;
+    return group_exchange(c, sends, nsend, recvs, nrecv, f->s);
+}
+
+/* The binomial tree to relrank 0 over p slots (reduce_intra_binomial.c:93-140:
+ * relrank r folds in the accumulation of r|mask as the second operand), slot
+ * r holding relrank r's vector; the result goes to `out`. */
+static int binomial_fold(const coll_t *f, char *scr, size_t slot, void *out, long count)
+{
+    int p = f->c->size, q, mask;
+    hipError_t e;
     if ((p & (p - 1)) == 0) {
         /* power of two: the binomial tree IS the pairwise tree ((x0+x1)+(x2+x3))+... */
+        const void *ys[MAX_RANKS];
         for (q = 0; q < p; q++)
             ys[q] = scr + (size_t) q * slot;
-        return fold_tree(ys, p, recvbuf, count, opidx, elem, s, fc);
+        return fold_tree(f, ys, p, out, count);
     }
     for (mask = 1; mask < p; mask <<= 1)
         for (q = 0; q + mask < p; q += 2 * mask)
-            if ((rc = fold_step(scr + (size_t) (q + mask) * slot, scr + (size_t) q * slot, count, opidx, elem,
-                                s, fc)) != MPI_SUCCESS)
-                return rc;
-    e = hipMemcpyAsync(recvbuf, scr, bytes, hipMemcpyDeviceToDevice, s);
-    return e == hipSuccess ? MPI_SUCCESS : hip_err(fc, e);
+            TRY(fold_step(f, scr + (size_t) (q + mask) * slot, scr + (size_t) q * slot, count));
+    e = hipMemcpyAsync(out, scr, (size_t) count * f->esz, hipMemcpyDeviceToDevice, f->s);
+    return e == hipSuccess ? MPI_SUCCESS : hip_err(f->fc, e);
+}
+
+/* MPI_Allreduce, count*size <= 2048 or count < pof2: MPIR_Reduce takes the
+ * binomial tree to root 0 (reduce.c:214-225, reduce_intra_binomial.c:93-140),
+ * then MPIR_Bcast.  Here: an allgather of the p inputs into slots 0..p-1, then
+ * every rank folds them in the binomial order itself, so all ranks hold root
+ * 0's bytes. */
+static int allreduce_short(const coll_t *f, const void *x, void *recvbuf, long count)
+{
+    size_t bytes = (size_t) count * f->esz;
+    char *scr = NULL;
+    TRY(allgather_slots(f, x, bytes, &scr));
+    return binomial_fold(f, scr, stage_stride(bytes), recvbuf, count);
 }
 
 /* MPI_Allreduce, flat branch, recursive doubling
@@ -639,44 +727,18 @@ static int allreduce_short(struct MPIX_Hip_comm_s *c, const void *sendbuf, void 
  * the partial of n ^ mask second, so n ends with the tree over z_j = Y_{n ^ j};
  * an excluded even rank receives the result of its odd neighbour.  Here: an
  * allgather of the p inputs, the rem pre-fold steps, one tree combine per rank. */
-static int allreduce_recursive_doubling(struct MPIX_Hip_comm_s *c, const void *sendbuf, void *recvbuf,
-                                        long count, size_t esz, int opidx, int elem, hipStream_t s,
-                                        const char *fc)
+static int allreduce_recursive_doubling(const coll_t *f, const void *x, void *recvbuf, long count)
 {
-    int p = c->size, q, nx = 0, rc = MPI_SUCCESS, pof2 = pof2_of(p), rem = p - pof2, n, j, m;
-    size_t bytes = (size_t) count * esz, slot = stage_stride(bytes);
-    xfer_t sends[MAX_XFER], recvs[MAX_XFER];
-    const void *ys[64];
-    char *scr = NULL, *own;
-    hipError_t e;
-    if (comm_scratch(c, (size_t) p * slot, &scr)) {
-        MPIR_Err_set_detail("%s: scratch allocation failed", fc);
-        return MPI_ERR_NO_MEM;
-    }
-    own = scr + (size_t) c->rank * slot;
-    e = hipMemcpyAsync(own, sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf, bytes, hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess)
-        return hip_err(fc, e);
-    for (q = 0; q < p; q++) {
-        if (q == c->rank)
-            continue;
-        sends[nx].buf = own;
-        sends[nx].bytes = bytes;
-        sends[nx].peer = q;
-        recvs[nx].buf = scr + (size_t) q * slot;
-        recvs[nx].bytes = bytes;
-        recvs[nx++].peer = q;
-    }
-    if ((rc = group_exchange(c, sends, nx, recvs, nx, s)) != MPI_SUCCESS)
-        return rc;
+    int p = f->c->size, pof2 = pof2_of(p), rem = p - pof2, n = newrank_of(f->c->rank, rem), j, m;
+    size_t bytes = (size_t) count * f->esz, slot = stage_stride(bytes);
+    const void *ys[MAX_RANKS];
+    char *scr = NULL;
+    TRY(allgather_slots(f, x, bytes, &scr));
     for (m = 0; m < rem; m++)
-        if ((rc = fold_step(scr + (size_t) (2 * m) * slot, scr + (size_t) (2 * m + 1) * slot, count, opidx,
-                            elem, s, fc)) != MPI_SUCCESS)
-            return rc;
-    n = c->rank < 2 * rem ? c->rank / 2 : c->rank - rem;
+        TRY(fold_step(f, scr + (size_t) (2 * m) * slot, scr + (size_t) (2 * m + 1) * slot, count));
     for (j = 0; j < pof2; j++)
         ys[j] = scr + (size_t) real_of(n ^ j, rem, 1) * slot;
-    return fold_tree(ys, pof2, recvbuf, count, opidx, elem, s, fc);
+    return fold_tree(f, ys, pof2, recvbuf, count);
 }
 
 /* MPI_Reduce_scatter(_block), total bytes < 524288: recursive halving
@@ -688,79 +750,43 @@ static int allreduce_recursive_doubling(struct MPIX_Hip_comm_s *c, const void *s
  *   mask = pof2/2 first, received data second).
  * Here: one all-to-all of blocks (every rank gets x_q's block r from each q),
  * the rem pre-fold steps, one tree combine into recvbuf. */
-static int reduce_scatter_short(struct MPIX_Hip_comm_s *c, const char *src, void *recvbuf, const long *cnts,
-                                const long *disps, size_t esz, int opidx, int elem, hipStream_t s, const char *fc)
+static int reduce_scatter_short(const coll_t *f, const char *src, void *recvbuf, const long *cnts,
+                                const long *disps)
 {
-    int p = c->size, q, nx = 0, rc = MPI_SUCCESS, pof2 = pof2_of(p), rem = p - pof2, bits = 0, n, k, m;
+    struct MPIX_Hip_comm_s *c = f->c;
+    int p = c->size, q, nsend = 0, nrecv = 0, pof2 = pof2_of(p), rem = p - pof2, bits = ilog2(pof2);
+    int n = newrank_of(c->rank, rem), k, m;
     long rcount = cnts[c->rank];
-    size_t nb = (size_t) rcount * esz, slot = stage_stride(nb);
+    size_t esz = f->esz, nb = (size_t) rcount * esz, slot = stage_stride(nb);
     xfer_t sends[MAX_XFER], recvs[MAX_XFER];
-    const void *ys[64];
+    const void *ys[MAX_RANKS];
     char *scr = NULL;
     hipError_t e;
-    while ((1 << bits) < pof2)
-        bits++;
-    if (comm_scratch(c, (size_t) p * slot + 256, &scr)) {
-        MPIR_Err_set_detail("%s: scratch allocation failed", fc);
-        return MPI_ERR_NO_MEM;
-    }
+    TRY(comm_scratch(c, (size_t) p * slot + 256, &scr, f->fc));
     /* own block into its slot: the pre-fold updates slots in place */
     if (nb) {
         e = hipMemcpyAsync(scr + (size_t) c->rank * slot, src + (size_t) disps[c->rank] * esz, nb,
-                           hipMemcpyDeviceToDevice, s);
+                           hipMemcpyDeviceToDevice, f->s);
         if (e != hipSuccess)
-            return hip_err(fc, e);
+            return hip_err(f->fc, e);
     }
     for (q = 0; q < p; q++) {
         if (q == c->rank)
             continue;
-        sends[nx].buf = (void *) (src + (size_t) disps[q] * esz);
-        sends[nx].bytes = (size_t) cnts[q] * esz;
-        sends[nx].peer = q;
-        recvs[nx].buf = scr + (size_t) q * slot;
-        recvs[nx].bytes = nb;
-        recvs[nx++].peer = q;
+        xfer_add(sends, &nsend, src + (size_t) disps[q] * esz, (size_t) cnts[q] * esz, q);
+        xfer_add(recvs, &nrecv, scr + (size_t) q * slot, nb, q);
     }
-    if ((rc = group_exchange(c, sends, nx, recvs, nx, s)) != MPI_SUCCESS)
-        return rc;
+    TRY(group_exchange(c, sends, nsend, recvs, nrecv, f->s));
     if (!rcount)
         return MPI_SUCCESS;
     for (m = 0; m < rem; m++)
-        if ((rc = fold_step(scr + (size_t) (2 * m) * slot, scr + (size_t) (2 * m + 1) * slot, rcount, opidx,
-                            elem, s, fc)) != MPI_SUCCESS)
-            return rc;
-    n = c->rank < 2 * rem ? c->rank / 2 : c->rank - rem;
-    for (k = 0; k < pof2; k++) {
-        int y = n ^ bitrev(k, bits);
-        ys[k] = scr + (size_t) (y < rem ? 2 * y + 1 : y + rem) * slot;
-    }
-    return fold_tree(ys, pof2, recvbuf, rcount, opidx, elem, s, fc);
+        TRY(fold_step(f, scr + (size_t) (2 * m) * slot, scr + (size_t) (2 * m + 1) * slot, rcount));
+    for (k = 0; k < pof2; k++)
+        ys[k] = scr + (size_t) real_of(n ^ bitrev(k, bits), rem, 1) * slot;
+    return fold_tree(f, ys, pof2, recvbuf, rcount);
 }
 
-/* the pipelined folds: operands and output shifted by the chunk's offset */
-typedef struct {
-    const void *const *ys;
-    int n, order, opidx, elem;
-    char *out;
-    size_t esz;
-    const char *fc;
-} fold_ctx_t;
-
-static int chunk_fold(void *ctx, size_t off, size_t len, hipStream_t fs)
-{
-    const fold_ctx_t *f = ctx;
-    const void *ys[64];
-    int i, rc;
-    for (i = 0; i < f->n; i++)
-        ys[i] = (const char *) f->ys[i] + off;
-    rc = MPIR_Hip_combine(ys, f->n, f->out + off, (uint64_t) (len / f->esz), f->opidx, f->elem, f->order, fs, 0);
-    if (rc) {
-        MPIR_Op_report_hip_error(f->fc, rc);
-        return MPI_ERR_OTHER;
-    }
-    return MPI_SUCCESS;
-}
-
+/* ------------------------------------------------------------ the call frame */
 /* validation shared by the collectives (MPIR_ERRTEST_OP + check_dtype) */
 static int coll_check(const char *fc, const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op,
                       MPIX_Hip_comm comm, int *elem)
@@ -794,16 +820,55 @@ static int coll_check(const char *fc, const void *sendbuf, void *recvbuf, int co
     return MPI_SUCCESS;
 }
 
-static int want_rccl(struct MPIX_Hip_comm_s *c, int algorithm, int elem, int opidx, ncclDataType_t * t,
-                     ncclRedOp_t * o)
+/* Opens the call f (fc and c set by the entry point): validates, with
+ * `recvbuf` the buffer that takes part in the alias check; then moves to the
+ * communicator's device and picks the stream.  Returns 0 when the entry point
+ * is to return *rc at once (an error, already final, or nothing to do),
+ * else 1: the schedule runs and its result goes through coll_end(). */
+static int coll_begin(coll_t *f, const void *sendbuf, void *recvbuf, int count, MPI_Datatype dt, MPI_Op op,
+                      void *hip_stream, int *rc)
+{
+    *rc = coll_check(f->fc, sendbuf, recvbuf, count, dt, op, f->c, &f->elem);
+    if (*rc)
+        *rc = MPIR_Err_return(f->fc, *rc);
+    if (*rc || count == 0)
+        return 0;
+    f->switched = hipGetDevice(&f->saved_device) == hipSuccess && f->saved_device != f->c->device;
+    if (f->switched)
+        (void) hipSetDevice(f->c->device);
+    f->user_stream = hip_stream != NULL;
+    f->s = hip_stream ? (hipStream_t) hip_stream : f->c->stream;
+    f->opidx = op & 0xf;
+    f->esz = MPIR_Hip_elem_size(f->elem);
+    return 1;
+}
+
+/* Closes the call with the schedule's result: a successful call on the
+ * communicator's own stream is synchronised (a caller's stream never is),
+ * the caller's device is put back if it was left. */
+static int coll_end(coll_t *f, int rc)
+{
+    if (rc == MPI_SUCCESS && !f->user_stream) {
+        hipError_t e = hipStreamSynchronize(f->s);
+        if (e != hipSuccess) {
+            MPIR_Err_set_detail("hipStreamSynchronize(s): %s", hipGetErrorString(e));
+            rc = MPI_ERR_OTHER;
+        }
+    }
+    if (f->switched)
+        (void) hipSetDevice(f->saved_device);
+    return rc ? MPIR_Err_return(f->fc, rc) : MPI_SUCCESS;
+}
+
+static int want_rccl(const coll_t *f, int algorithm, ncclDataType_t * t, ncclRedOp_t * o)
 {
     const char *v;
-    if (c->kind != COMM_RCCL || algorithm == MPIX_HIP_ALG_REFERENCE_ORDER)
+    if (f->c->kind != COMM_RCCL || algorithm == MPIX_HIP_ALG_REFERENCE_ORDER)
         return 0;
     if (algorithm == MPIX_HIP_ALG_AUTO && (v = getenv("MPIR_CVAR_DEVICE_COLL_ALGORITHM")) &&
         !strcmp(v, "reference"))
         return 0;
-    switch (elem) {
+    switch (f->elem) {
     case MPIR_HIP_I8: *t = ncclInt8; break;
     case MPIR_HIP_U8: *t = ncclUint8; break;
     case MPIR_HIP_I32: *t = ncclInt32; break;
@@ -815,7 +880,7 @@ static int want_rccl(struct MPIX_Hip_comm_s *c, int algorithm, int elem, int opi
     case MPIR_HIP_F64: *t = ncclFloat64; break;
     default: return 0;
     }
-    switch (opidx) {
+    switch (f->opidx) {
     case MPIR_HIP_OP_SUM: *o = ncclSum; break;
     case MPIR_HIP_OP_PROD: *o = ncclProd; break;
     case MPIR_HIP_OP_MAX: *o = ncclMax; break;
@@ -825,9 +890,60 @@ static int want_rccl(struct MPIX_Hip_comm_s *c, int algorithm, int elem, int opi
     return 1;
 }
 
-#define HIPTRY(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
-        MPIR_Err_set_detail("%s: %s", #x, hipGetErrorString(e_)); rc = MPI_ERR_OTHER; goto done; } } while (0)
-#define TRY(x) do { if ((rc = (x)) != MPI_SUCCESS) goto done; } while (0)
+/* ------------------------------------------------------------ reduce-scatter / gather
+ * The layout of reduce_intra_reduce_scatter_gather.c and allreduce_intra_
+ * reduce_scatter_allgather.c for one rank: `count` elements in pof2 blocks
+ * (the first count % pof2 one element longer), newrank n owning block
+ * bitrev(n); the staging for the blocks a rank receives. */
+typedef struct {
+    int pof2, rem, bits;
+    int odd_keeps;              /* the pre-fold's keeper of pair m: 2m+1, else 2m (real_of) */
+    int newrank;                /* this rank's; -1: excluded by the pre-fold */
+    long cnts[MAX_RANKS], disps[MAX_RANKS];     /* of block b, in elements */
+    size_t esz;
+    size_t blk;                 /* stride of the staging slots: stage_stride of the largest block, cnts[0] */
+    size_t tmp_off;             /* the pre-fold partner's vector in scratch, behind the pof2-1 slots */
+    int nchunk;                 /* the all-to-all's pipeline (pipe_chunks): every rank derives */
+    size_t chunk;               /* the same chunk count from the largest block */
+} rsg_t;
+
+static void rsg_layout(rsg_t *g, int p, int rank, long count, size_t esz, int odd_keeps)
+{
+    int i;
+    g->pof2 = pof2_of(p);
+    g->rem = p - g->pof2;
+    g->bits = ilog2(g->pof2);
+    g->odd_keeps = odd_keeps;
+    g->newrank = rank < 2 * g->rem && (rank % 2) != (odd_keeps ? 1 : 0) ? -1 : newrank_of(rank, g->rem);
+    for (i = 0; i < g->pof2; i++)
+        g->cnts[i] = count / g->pof2 + (i < count % g->pof2 ? 1 : 0);
+    g->disps[0] = 0;
+    for (i = 1; i < g->pof2; i++)
+        g->disps[i] = g->disps[i - 1] + g->cnts[i - 1];
+    g->esz = esz;
+    g->blk = stage_stride((size_t) g->cnts[0] * esz);
+    g->tmp_off = (size_t) (g->pof2 > 1 ? g->pof2 - 1 : 1) * g->blk;
+    g->chunk = 0;
+    g->nchunk = g->pof2 > 1 ? pipe_chunks((size_t) g->cnts[0] * esz, &g->chunk) : 1;
+}
+
+/* block b of a vector laid out by g: its byte offset and length */
+static size_t rsg_off(const rsg_t *g, int b)
+{
+    return (size_t) g->disps[b] * g->esz;
+}
+
+static size_t rsg_len(const rsg_t *g, int b)
+{
+    return (size_t) g->cnts[b] * g->esz;
+}
+
+/* what rsg_phase needs in `scr` for a vector of `bytes`: the slots, then the
+ * pre-fold partner's vector */
+static size_t rsg_scratch_bytes(const rsg_t *g, size_t bytes)
+{
+    return g->tmp_off + bytes + 256;
+}
 
 /* The reduce-scatter phase of reduce_intra_reduce_scatter_gather.c on `work`
  * (count elements, this rank's contribution): the non-power-of-two pre-fold
@@ -836,206 +952,152 @@ static int want_rccl(struct MPIX_Hip_comm_s *c, int algorithm, int elem, int opi
  * fused tree combine: newrank n owns block bitrev(n), reduced as
  * ((y0+y1)+(y2+y3))+... with y_j = the block from newrank n ^ j.
  * `scr` holds rsg_scratch_bytes(): (pof2-1) slots of stage_stride(cnts[0]
- * elements), then `count` elements for the pre-fold partner's vector.
- * Returns this rank's newrank in *newrank (-1: excluded by the pre-fold). */
-
-static size_t rsg_scratch_bytes(int pof2, const long *cnts, size_t esz, size_t bytes)
+ * elements), then `count` elements for the pre-fold partner's vector. */
+static int rsg_phase(const coll_t *f, const rsg_t *g, char *work, long count, char *scr)
 {
-    return (size_t) (pof2 > 1 ? pof2 - 1 : 1) * stage_stride((size_t) cnts[0] * esz) + bytes + 256;
-}
-
-static int rsg_phase(struct MPIX_Hip_comm_s *c, char *work, long count, size_t esz, int opidx, int elem,
-                     hipStream_t s, const char *fc, char *scr, const long *cnts, const long *disps, int odd_keeps,
-                     int *newrank, int *nchunk, size_t *chunk)
-{
-    int p = c->size, pof2 = pof2_of(p), rem = p - pof2, bits = 0, nsend = 0, nrecv = 0, rc, i;
-    size_t bytes = (size_t) count * esz, blk = stage_stride((size_t) cnts[0] * esz);
+    struct MPIX_Hip_comm_s *c = f->c;
+    hipStream_t s = f->s;
+    int pof2 = g->pof2, rem = g->rem, n = g->newrank, mb = n >= 0 ? bitrev(n, g->bits) : 0;
+    int nsend = 0, nrecv = 0, i, m;
+    size_t bytes = (size_t) count * f->esz;
     xfer_t sends[MAX_XFER], recvs[MAX_XFER];
-    while ((1 << bits) < pof2)
-        bits++;
-    /* pre-fold; every rank takes part in the transfer group (empty for ranks >= 2*rem).
-     * The keeper folds its partner's vector in as the second operand. */
-    if (rem > 0 && c->rank >= 2 * rem)
-        if ((rc = group_exchange(c, NULL, 0, NULL, 0, s)) != MPI_SUCCESS)
-            return rc;
-    if (c->rank < 2 * rem) {
-        const int keeper = (c->rank % 2) == (odd_keeps ? 1 : 0);
-        if (!keeper) {
-            xfer_t x = { work, bytes, odd_keeps ? c->rank + 1 : c->rank - 1 };
-            if ((rc = group_exchange(c, &x, 1, NULL, 0, s)) != MPI_SUCCESS)
-                return rc;
-            *newrank = -1;
-        } else {
-            char *tmp = scr + (size_t) (pof2 > 1 ? pof2 - 1 : 1) * blk;
-            xfer_t x = { tmp, bytes, odd_keeps ? c->rank - 1 : c->rank + 1 };
-            if ((rc = group_exchange(c, NULL, 0, &x, 1, s)) != MPI_SUCCESS)
-                return rc;
-            if ((rc = fold_step(tmp, work, count, opidx, elem, s, fc)) != MPI_SUCCESS)
-                return rc;
-            *newrank = c->rank / 2;
-        }
-    } else
-        *newrank = c->rank - rem;
+    const void *ys[MAX_RANKS];
+    fold_ctx_t fo = { ys, pof2, MPIR_HIP_ORDER_TREE, NULL, 0 };   /* (an excluded rank folds nothing) */
+    /* pre-fold; every rank takes part in the transfer group (empty for ranks >= 2*rem):
+     * of the pair (2m, 2m+1) one sends its vector, the keeper receives it and
+     * folds it in as the second operand. */
+    if (rem > 0) {
+        const int paired = c->rank < 2 * rem, keeper = paired && g->newrank >= 0;
+        char *tmp = scr + g->tmp_off;
+        xfer_t x = { keeper ? tmp : work, bytes, c->rank ^ 1 };
+        TRY(group_exchange(c, &x, paired && !keeper, &x, keeper, s));
+        if (keeper)
+            TRY(fold_step(f, tmp, work, count));
+    }
 
     /* all-to-all of blocks: the owner receives y_j into scratch slot j-1;
      * chunked, with the tree folded chunk by chunk behind it, when the blocks
-     * are large (pipe_chunks: every rank derives the same chunk count from
-     * the largest block, cnts[0]) */
-    *nchunk = pof2 > 1 ? pipe_chunks((size_t) cnts[0] * esz, chunk) : 1;
-    if (*nchunk > 1 && (rc = pipe_init(c)) != MPI_SUCCESS)
-        return rc;
-    if (*newrank >= 0 && pof2 > 1) {
-        int n = *newrank, mb = bitrev(n, bits), m;
-        const void *ys[64];
+     * are large (g->nchunk).  A rank the pre-fold excluded matches the group
+     * calls of the others with no transfers and folds nothing. */
+    if (pof2 == 1)
+        return MPI_SUCCESS;
+    if (g->nchunk > 1)
+        TRY(pipe_init(c));
+    if (n >= 0) {
         for (m = 0; m < pof2; m++) {
-            int real, b;
+            int real = real_of(m, rem, g->odd_keeps), b = bitrev(m, g->bits);
             if (m == n)
                 continue;
-            real = real_of(m, rem, odd_keeps);
-            b = bitrev(m, bits);
-            sends[nsend].buf = work + disps[b] * esz;
-            sends[nsend].bytes = (size_t) cnts[b] * esz;
-            sends[nsend++].peer = real;
-            recvs[nrecv].buf = scr + (size_t) ((n ^ m) - 1) * blk;
-            recvs[nrecv].bytes = (size_t) cnts[mb] * esz;
-            recvs[nrecv++].peer = real;
+            xfer_add(sends, &nsend, work + rsg_off(g, b), rsg_len(g, b), real);
+            xfer_add(recvs, &nrecv, scr + (size_t) ((n ^ m) - 1) * g->blk, rsg_len(g, mb), real);
         }
-        ys[0] = work + disps[mb] * esz;
+        ys[0] = fo.out = work + rsg_off(g, mb);
         for (i = 1; i < pof2; i++)
-            ys[i] = scr + (size_t) (i - 1) * blk;
-        if (*nchunk > 1) {
-            fold_ctx_t f = { ys, pof2, MPIR_HIP_ORDER_TREE, opidx, elem, work + disps[mb] * esz, esz, fc };
-            return exchange_fold_pipelined(c, sends, nsend, recvs, nrecv, *nchunk, *chunk, (size_t) cnts[mb] * esz,
-                                           s, chunk_fold, &f);
-        }
-        if ((rc = group_exchange(c, sends, nsend, recvs, nrecv, s)) != MPI_SUCCESS)
-            return rc;
-        if (cnts[mb] && (rc = fold_tree(ys, pof2, work + disps[mb] * esz, cnts[mb], opidx, elem, s, fc)))
-            return rc;
-    } else if (pof2 > 1) {
-        /* excluded rank: matches the group calls of the participants (no transfers) */
-        if (*nchunk > 1)
-            return exchange_fold_pipelined(c, NULL, 0, NULL, 0, *nchunk, *chunk, 0, s, chunk_fold, NULL);
-        if ((rc = group_exchange(c, NULL, 0, NULL, 0, s)) != MPI_SUCCESS)
-            return rc;
+            ys[i] = scr + (size_t) (i - 1) * g->blk;
+        fo.out_bytes = rsg_len(g, mb);
     }
-    return MPI_SUCCESS;
+    if (g->nchunk > 1)
+        return exchange_fold_pipelined(f, sends, nsend, recvs, nrecv, g->nchunk, g->chunk, &fo);
+    TRY(group_exchange(c, sends, nsend, recvs, nrecv, s));
+    return fo.out_bytes ? fold_tree(f, ys, pof2, fo.out, g->cnts[mb]) : MPI_SUCCESS;
+}
+
+/* one receive per reduced block of `buf`, from the rank that owns it */
+static void rsg_recv_blocks(const rsg_t *g, char *buf, int rank, xfer_t *recvs, int *nrecv)
+{
+    int i;
+    for (i = 0; i < g->pof2; i++) {
+        int real = real_of(i, g->rem, g->odd_keeps), b = bitrev(i, g->bits);
+        if (real != rank)
+            xfer_add(recvs, nrecv, buf + rsg_off(g, b), rsg_len(g, b), real);
+    }
+}
+
+/* The allgather of the reduced blocks of `buf` to every rank (the gather +
+ * MPIR_Bcast of allreduce_intra_smp.c move data only); chunk k of the owners'
+ * blocks leaves once its fold is done. */
+static int rsg_allgather(const coll_t *f, const rsg_t *g, char *buf)
+{
+    struct MPIX_Hip_comm_s *c = f->c;
+    xfer_t sends[MAX_XFER], recvs[MAX_XFER];
+    int nsend = 0, nrecv = 0, q;
+    if (g->newrank >= 0) {
+        int mb = bitrev(g->newrank, g->bits);
+        for (q = 0; q < c->size; q++)
+            if (q != c->rank)
+                xfer_add(sends, &nsend, buf + rsg_off(g, mb), rsg_len(g, mb), q);
+    }
+    rsg_recv_blocks(g, buf, c->rank, recvs, &nrecv);
+    if (g->nchunk > 1)
+        return exchange_after_folds(f, sends, nsend, recvs, nrecv, g->nchunk, g->chunk);
+    return group_exchange(c, sends, nsend, recvs, nrecv, f->s);
+}
+
+/* The gather of the owners' blocks to `root`, into its recvbuf
+ * (reduce_intra_reduce_scatter_gather.c:256-410). */
+static int rsg_gather(const coll_t *f, const rsg_t *g, char *work, char *recvbuf, int root)
+{
+    struct MPIX_Hip_comm_s *c = f->c;
+    xfer_t sends[MAX_XFER], recvs[MAX_XFER];
+    int nsend = 0, nrecv = 0;
+    if (c->rank == root)
+        rsg_recv_blocks(g, recvbuf, root, recvs, &nrecv);
+    else if (g->newrank >= 0) {
+        int mb = bitrev(g->newrank, g->bits);
+        xfer_add(sends, &nsend, work + rsg_off(g, mb), rsg_len(g, mb), root);
+    }
+    return group_exchange(c, sends, nsend, recvs, nrecv, f->s);
 }
 
 /* ------------------------------------------------------------ Allreduce */
-int MPIX_Allreduce_hip(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype, MPI_Op op,
-                       MPIX_Hip_comm comm, int algorithm, void *hip_stream)
+static int allreduce_schedule(const coll_t *f, const void *sendbuf, void *recvbuf, int count, int algorithm)
 {
-    static const char *fc = "MPIX_Allreduce_hip";
-    struct MPIX_Hip_comm_s *c = comm;
-    int elem = 0, opidx = op & 0xf, rc, p, pof2, rem, newrank = -1, bits, i, flat, odd_keeps, nchunk = 1, k;
-    size_t esz, bytes, chunk = 0;
-    hipStream_t s;
+    struct MPIX_Hip_comm_s *c = f->c;
+    const void *own = sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf;
+    size_t bytes = (size_t) count * f->esz;
+    int p = c->size, pof2 = pof2_of(p), flat;
     ncclDataType_t nt;
     ncclRedOp_t no;
-    long cnts[64] = {0}, disps[64] = {0};
-    xfer_t sends[MAX_XFER], recvs[MAX_XFER];
-    int nsend = 0, nrecv = 0, cur = 0;
+    rsg_t g;
     char *scr = NULL;
 
-    rc = coll_check(fc, sendbuf, recvbuf, count, datatype, op, comm, &elem);
-    if (rc)
-        return MPIR_Err_return(fc, rc);
-    if (count == 0)
-        return MPI_SUCCESS;
-    if (hipGetDevice(&cur) == hipSuccess && cur != c->device)
-        (void) hipSetDevice(c->device);
-    s = hip_stream ? (hipStream_t) hip_stream : c->stream;
-    esz = MPIR_Hip_elem_size(elem);
-    bytes = (size_t) count * esz;
-    p = c->size;
-
-    if (want_rccl(c, algorithm, elem, opidx, &nt, &no)) {
-        ncclResult_t r = rccl.AllReduce(sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf, recvbuf, (size_t) count,
-                                        nt, no, c->nccl, s);
-        if (r != ncclSuccess) {
-            MPIR_Err_set_detail("ncclAllReduce: %s", rccl.GetErrorString ? rccl.GetErrorString(r) : "?");
-            rc = MPI_ERR_OTHER;
-        }
-        goto done_sync;
+    if (want_rccl(f, algorithm, &nt, &no)) {
+        ncclResult_t r = rccl.AllReduce(own, recvbuf, (size_t) count, nt, no, c->nccl, f->s);
+        return r == ncclSuccess ? MPI_SUCCESS : rccl_err("ncclAllReduce", r);
     }
 
     /* ---- reference order: MPIR_Allreduce_intra_auto (allreduce.c:145-217).  On one
      * node the SMP branch runs (allreduce_intra_smp.c: MPIR_Reduce with
      * MPIR_Reduce_intra_auto's choice, then MPIR_Bcast); with the SMP CVARs off
      * (or a comm with one rank per node) the flat branch runs */
-    pof2 = pof2_of(p);
     if (p == 1) {
         if (sendbuf != MPI_IN_PLACE)
-            HIPTRY(hipMemcpyAsync(recvbuf, sendbuf, bytes, hipMemcpyDeviceToDevice, s));
-        goto done_sync;
+            HIPTRY(hipMemcpyAsync(recvbuf, sendbuf, bytes, hipMemcpyDeviceToDevice, f->s));
+        return MPI_SUCCESS;
     }
     flat = allreduce_flat_choice(bytes, count, pof2);
-    if (flat == FLAT_RECURSIVE_DOUBLING) {
-        TRY(allreduce_recursive_doubling(c, sendbuf, recvbuf, count, esz, opidx, elem, s, fc));
-        goto done_sync;
-    }
-    odd_keeps = flat == FLAT_RABENSEIFNER;
-    if (!flat && (bytes <= REDUCE_SHORT_MSG_SIZE || count < pof2)) {
-        TRY(allreduce_short(c, sendbuf, recvbuf, count, esz, opidx, elem, s, fc));
-        goto done_sync;
-    }
+    if (flat == FLAT_RECURSIVE_DOUBLING)
+        return allreduce_recursive_doubling(f, own, recvbuf, count);
+    if (!flat && (bytes <= REDUCE_SHORT_MSG_SIZE || count < pof2))
+        return allreduce_short(f, own, recvbuf, count);
     /* long: the reduce-scatter of reduce_intra_reduce_scatter_gather.c (SMP) or
      * allreduce_intra_reduce_scatter_allgather.c (flat, Rabenseifner) on recvbuf */
     if (sendbuf != MPI_IN_PLACE)
-        HIPTRY(hipMemcpyAsync(recvbuf, sendbuf, bytes, hipMemcpyDeviceToDevice, s));
-    rem = p - pof2;
-    bits = 0;
-    while ((1 << bits) < pof2)
-        bits++;
-    cnts_disps(count, pof2, cnts, disps);
-    if (comm_scratch(c, rsg_scratch_bytes(pof2, cnts, esz, bytes), &scr)) {
-        MPIR_Err_set_detail("%s: scratch allocation failed", fc);
-        rc = MPI_ERR_NO_MEM;
-        goto done;
-    }
-    TRY(rsg_phase(c, recvbuf, count, esz, opidx, elem, s, fc, scr, cnts, disps, odd_keeps, &newrank, &nchunk, &chunk));
+        HIPTRY(hipMemcpyAsync(recvbuf, sendbuf, bytes, hipMemcpyDeviceToDevice, f->s));
+    rsg_layout(&g, p, c->rank, count, f->esz, flat == FLAT_RABENSEIFNER);
+    TRY(comm_scratch(c, rsg_scratch_bytes(&g, bytes), &scr, f->fc));
+    TRY(rsg_phase(f, &g, recvbuf, count, scr));
+    return rsg_allgather(f, &g, recvbuf);
+}
 
-    /* allgather of the reduced blocks to every rank (the gather + MPIR_Bcast of
-     * allreduce_intra_smp.c move data only) */
-    nsend = nrecv = 0;
-    if (newrank >= 0) {
-        int mb = bitrev(newrank, bits), q;
-        for (q = 0; q < p; q++) {
-            if (q == c->rank)
-                continue;
-            sends[nsend].buf = (char *) recvbuf + disps[mb] * esz;
-            sends[nsend].bytes = (size_t) cnts[mb] * esz;
-            sends[nsend++].peer = q;
-        }
-    }
-    for (i = 0; i < pof2; i++) {
-        int real = real_of(i, rem, odd_keeps), b = bitrev(i, bits);
-        if (real == c->rank)
-            continue;
-        recvs[nrecv].buf = (char *) recvbuf + disps[b] * esz;
-        recvs[nrecv].bytes = (size_t) cnts[b] * esz;
-        recvs[nrecv++].peer = real;
-    }
-    if (nchunk > 1) {
-        /* chunk k of the owners' blocks leaves once its fold is done */
-        xfer_t sk[MAX_XFER], rk[MAX_XFER];
-        for (k = 0; k < nchunk; k++) {
-            HIPTRY(hipStreamWaitEvent(s, c->fev[k], 0));
-            chunk_of(sends, nsend, k, chunk, sk);
-            chunk_of(recvs, nrecv, k, chunk, rk);
-            TRY(group_exchange(c, sk, nsend, rk, nrecv, s));
-        }
-    } else
-        TRY(group_exchange(c, sends, nsend, recvs, nrecv, s));
-
-  done_sync:
-    if (rc == MPI_SUCCESS && !hip_stream)
-        HIPTRY(hipStreamSynchronize(s));
-  done:
-    if (cur != c->device)
-        (void) hipSetDevice(cur);
-    return rc ? MPIR_Err_return(fc, rc) : MPI_SUCCESS;
+int MPIX_Allreduce_hip(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype, MPI_Op op,
+                       MPIX_Hip_comm comm, int algorithm, void *hip_stream)
+{
+    coll_t f = { .fc = "MPIX_Allreduce_hip", .c = comm };
+    int rc;
+    if (!coll_begin(&f, sendbuf, recvbuf, count, datatype, op, hip_stream, &rc))
+        return rc;
+    return coll_end(&f, allreduce_schedule(&f, sendbuf, recvbuf, count, algorithm));
 }
 
 /* ------------------------------------------------------------ Reduce
@@ -1047,140 +1109,76 @@ int MPIX_Allreduce_hip(const void *sendbuf, void *recvbuf, int count, MPI_Dataty
  *   else reduce_intra_reduce_scatter_gather.c: the reduce-scatter phase of the
  *       Allreduce (block values do not depend on the root), then the owners'
  *       blocks are gathered to the root. */
-int MPIX_Reduce_hip(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype, MPI_Op op, int root,
-                    MPIX_Hip_comm comm, int algorithm, void *hip_stream)
+static int reduce_schedule(const coll_t *f, const void *sendbuf, void *recvbuf, int count, int root, int algorithm)
 {
-    static const char *fc = "MPIX_Reduce_hip";
-    struct MPIX_Hip_comm_s *c = comm;
-    int elem = 0, opidx = op & 0xf, rc, p, pof2, rem, newrank = -1, bits, i, isroot, cur = 0, nchunk = 1;
-    size_t esz, bytes, slot, chunk = 0;
-    hipStream_t s;
+    struct MPIX_Hip_comm_s *c = f->c;
+    const void *own = sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf;
+    size_t bytes = (size_t) count * f->esz, slot;
+    int p = c->size, pof2 = pof2_of(p), isroot = c->rank == root, i;
+    hipStream_t s = f->s;
     ncclDataType_t nt;
     ncclRedOp_t no;
-    long cnts[64] = {0}, disps[64] = {0};
-    xfer_t sends[MAX_XFER], recvs[MAX_XFER];
-    int nsend = 0, nrecv = 0;
+    rsg_t g;
     char *scr = NULL, *work;
-    const void *own;
 
-    if (comm && (root < 0 || root >= comm->size)) {
-        MPIR_Err_set_detail("%s: Invalid root (value given was %d)", fc, root);
-        return MPIR_Err_return(fc, MPI_ERR_ROOT);
-    }
-    isroot = comm && comm->rank == root;
-    if (comm && !isroot && sendbuf == MPI_IN_PLACE && count > 0) {
-        MPIR_Err_set_detail("%s: MPI_IN_PLACE is only valid at the root", fc);
-        return MPIR_Err_return(fc, MPI_ERR_BUFFER);
-    }
-    /* recvbuf is significant at the root only (the alias check with it too) */
-    rc = coll_check(fc, sendbuf, isroot ? recvbuf : NULL, count, datatype, op, comm, &elem);
-    if (rc)
-        return MPIR_Err_return(fc, rc);
-    if (count == 0)
-        return MPI_SUCCESS;
-    if (hipGetDevice(&cur) == hipSuccess && cur != c->device)
-        (void) hipSetDevice(c->device);
-    s = hip_stream ? (hipStream_t) hip_stream : c->stream;
-    esz = MPIR_Hip_elem_size(elem);
-    bytes = (size_t) count * esz;
-    p = c->size;
-    own = sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf;
-
-    if (want_rccl(c, algorithm, elem, opidx, &nt, &no)) {
+    if (want_rccl(f, algorithm, &nt, &no)) {
         ncclResult_t r = rccl.Reduce(own, isroot ? recvbuf : NULL, (size_t) count, nt, no, root, c->nccl, s);
-        if (r != ncclSuccess) {
-            MPIR_Err_set_detail("ncclReduce: %s", rccl.GetErrorString ? rccl.GetErrorString(r) : "?");
-            rc = MPI_ERR_OTHER;
-        }
-        goto done_sync;
+        return r == ncclSuccess ? MPI_SUCCESS : rccl_err("ncclReduce", r);
     }
-
-    pof2 = pof2_of(p);
     if (p == 1) {
         if (sendbuf != MPI_IN_PLACE)
             HIPTRY(hipMemcpyAsync(recvbuf, sendbuf, bytes, hipMemcpyDeviceToDevice, s));
-        goto done_sync;
+        return MPI_SUCCESS;
     }
     if (bytes <= REDUCE_SHORT_MSG_SIZE || count < pof2) {
         /* binomial: slot rel holds x_{(rel + root) % p}; the tree folds relranks */
-        int mask;
+        xfer_t recvs[MAX_XFER];
+        int nrecv = 0;
         slot = stage_stride(bytes);
         if (!isroot) {
             xfer_t x = { (void *) own, bytes, root };
-            TRY(group_exchange(c, &x, 1, NULL, 0, s));
-            goto done_sync;
+            return group_exchange(c, &x, 1, NULL, 0, s);
         }
-        if (comm_scratch(c, (size_t) p * slot, &scr)) {
-            MPIR_Err_set_detail("%s: scratch allocation failed", fc);
-            rc = MPI_ERR_NO_MEM;
-            goto done;
-        }
+        TRY(comm_scratch(c, (size_t) p * slot, &scr, f->fc));
         HIPTRY(hipMemcpyAsync(scr, own, bytes, hipMemcpyDeviceToDevice, s));
-        for (i = 1; i < p; i++) {
-            recvs[nrecv].buf = scr + (size_t) i * slot;
-            recvs[nrecv].bytes = bytes;
-            recvs[nrecv++].peer = (i + root) % p;
-        }
+        for (i = 1; i < p; i++)
+            xfer_add(recvs, &nrecv, scr + (size_t) i * slot, bytes, (i + root) % p);
         TRY(group_exchange(c, NULL, 0, recvs, nrecv, s));
-        if ((p & (p - 1)) == 0) {
-            const void *ys[64];
-            for (i = 0; i < p; i++)
-                ys[i] = scr + (size_t) i * slot;
-            TRY(fold_tree(ys, p, recvbuf, count, opidx, elem, s, fc));
-            goto done_sync;
-        }
-        for (mask = 1; mask < p; mask <<= 1)
-            for (i = 0; i + mask < p; i += 2 * mask)
-                TRY(fold_step(scr + (size_t) (i + mask) * slot, scr + (size_t) i * slot, count, opidx, elem, s, fc));
-        HIPTRY(hipMemcpyAsync(recvbuf, scr, bytes, hipMemcpyDeviceToDevice, s));
-        goto done_sync;
+        return binomial_fold(f, scr, slot, recvbuf, count);
     }
 
     /* long: reduce-scatter on `work` (recvbuf at the root, scratch elsewhere) */
-    rem = p - pof2;
-    bits = 0;
-    while ((1 << bits) < pof2)
-        bits++;
-    cnts_disps(count, pof2, cnts, disps);
-    slot = (rsg_scratch_bytes(pof2, cnts, esz, bytes) + 255) & ~(size_t) 255;
-    if (comm_scratch(c, slot + (isroot ? 0 : bytes), &scr)) {
-        MPIR_Err_set_detail("%s: scratch allocation failed", fc);
-        rc = MPI_ERR_NO_MEM;
-        goto done;
-    }
+    rsg_layout(&g, p, c->rank, count, f->esz, 0);
+    slot = (rsg_scratch_bytes(&g, bytes) + 255) & ~(size_t) 255;
+    TRY(comm_scratch(c, slot + (isroot ? 0 : bytes), &scr, f->fc));
     work = isroot ? (char *) recvbuf : scr + slot;
     if (work != own)
         HIPTRY(hipMemcpyAsync(work, own, bytes, hipMemcpyDeviceToDevice, s));
-    TRY(rsg_phase(c, work, count, esz, opidx, elem, s, fc, scr, cnts, disps, 0, &newrank, &nchunk, &chunk));
-    if (nchunk > 1)
-        HIPTRY(hipStreamWaitEvent(s, c->fev[nchunk - 1], 0));       /* every fold done */
+    TRY(rsg_phase(f, &g, work, count, scr));
+    if (g.nchunk > 1)
+        HIPTRY(hipStreamWaitEvent(s, c->fev[g.nchunk - 1], 0));     /* every fold done */
+    return rsg_gather(f, &g, work, recvbuf, root);
+}
 
-    /* gather of the owners' blocks to the root (reduce_intra_reduce_scatter_gather.c:256-410) */
-    if (newrank >= 0 && !isroot) {
-        int mb = bitrev(newrank, bits);
-        sends[nsend].buf = work + disps[mb] * esz;
-        sends[nsend].bytes = (size_t) cnts[mb] * esz;
-        sends[nsend++].peer = root;
-    }
-    if (isroot) {
-        for (i = 0; i < pof2; i++) {
-            int real = real_of(i, rem, 0), b = bitrev(i, bits);
-            if (real == c->rank)
-                continue;
-            recvs[nrecv].buf = (char *) recvbuf + disps[b] * esz;
-            recvs[nrecv].bytes = (size_t) cnts[b] * esz;
-            recvs[nrecv++].peer = real;
-        }
-    }
-    TRY(group_exchange(c, sends, nsend, recvs, nrecv, s));
+int MPIX_Reduce_hip(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype, MPI_Op op, int root,
+                    MPIX_Hip_comm comm, int algorithm, void *hip_stream)
+{
+    coll_t f = { .fc = "MPIX_Reduce_hip", .c = comm };
+    int rc, isroot;
 
-  done_sync:
-    if (rc == MPI_SUCCESS && !hip_stream)
-        HIPTRY(hipStreamSynchronize(s));
-  done:
-    if (cur != c->device)
-        (void) hipSetDevice(cur);
-    return rc ? MPIR_Err_return(fc, rc) : MPI_SUCCESS;
+    if (comm && (root < 0 || root >= comm->size)) {
+        MPIR_Err_set_detail("%s: Invalid root (value given was %d)", f.fc, root);
+        return MPIR_Err_return(f.fc, MPI_ERR_ROOT);
+    }
+    isroot = comm && comm->rank == root;
+    if (comm && !isroot && sendbuf == MPI_IN_PLACE && count > 0) {
+        MPIR_Err_set_detail("%s: MPI_IN_PLACE is only valid at the root", f.fc);
+        return MPIR_Err_return(f.fc, MPI_ERR_BUFFER);
+    }
+    /* recvbuf is significant at the root only (the alias check with it too) */
+    if (!coll_begin(&f, sendbuf, isroot ? recvbuf : NULL, count, datatype, op, hip_stream, &rc))
+        return rc;
+    return coll_end(&f, reduce_schedule(&f, sendbuf, recvbuf, count, root, algorithm));
 }
 
 /* ------------------------------------------------------------ Reduce_scatter(_block)
@@ -1191,77 +1189,38 @@ int MPIX_Reduce_hip(const void *sendbuf, void *recvbuf, int count, MPI_Datatype 
  *   (reduce_scatter_block_intra_pairwise.c:97-134 /
  *   reduce_scatter_intra_pairwise.c): block r = ((x_r + x_{r-1}) + x_{r-2}) + ...
  *   as one all-to-all + one CHAIN combine. */
-static int reduce_scatter_common(const char *fc, const void *sendbuf, void *recvbuf, const int *counts,
-                                 MPI_Datatype datatype, MPI_Op op, MPIX_Hip_comm comm, int algorithm,
-                                 void *hip_stream)
+static int reduce_scatter_schedule(const coll_t *f, const void *sendbuf, void *recvbuf, const long *cnts,
+                                   const long *disps, int regular, int algorithm)
 {
-    struct MPIX_Hip_comm_s *c = comm;
-    int elem = 0, opidx = op & 0xf, rc, p, i, cur = 0, regular = 1;
-    long cnts[64] = {0}, disps[64] = {0}, total = 0;
-    size_t esz, nb, slot;
-    hipStream_t s;
+    struct MPIX_Hip_comm_s *c = f->c;
+    int p = c->size, i, nsend = 0, nrecv = 0, nchunk;
+    long total = disps[p - 1] + cnts[p - 1];
+    size_t esz = f->esz, nb = (size_t) cnts[c->rank] * esz, slot, maxb = 0, chunk = 0;
+    hipStream_t s = f->s;
     ncclDataType_t nt;
     ncclRedOp_t no;
     xfer_t sends[MAX_XFER], recvs[MAX_XFER];
-    const void *ys[64];
-    const char *src;
+    const void *ys[MAX_RANKS];
+    const char *src = sendbuf == MPI_IN_PLACE ? (const char *) recvbuf : (const char *) sendbuf;
     char *scr = NULL;
 
-    if (!comm) {
-        MPIR_Err_set_detail("%s: null communicator", fc);
-        return MPIR_Err_return(fc, MPI_ERR_ARG);
-    }
-    p = c->size;
-    for (i = 0; i < p; i++) {
-        if (counts[i] < 0) {
-            MPIR_Err_set_detail("%s: negative count", fc);
-            return MPIR_Err_return(fc, MPI_ERR_COUNT);
-        }
-        cnts[i] = counts[i];
-        disps[i] = total;
-        total += counts[i];
-        regular &= counts[i] == counts[0];
-    }
-    /* op / type validation; the alias check applies when any data moves */
-    rc = coll_check(fc, sendbuf, recvbuf, total > 0, datatype, op, comm, &elem);
-    if (rc)
-        return MPIR_Err_return(fc, rc);
-    if (total == 0)
-        return MPI_SUCCESS;
-    if (hipGetDevice(&cur) == hipSuccess && cur != c->device)
-        (void) hipSetDevice(c->device);
-    s = hip_stream ? (hipStream_t) hip_stream : c->stream;
-    esz = MPIR_Hip_elem_size(elem);
-    nb = (size_t) cnts[c->rank] * esz;
-    src = sendbuf == MPI_IN_PLACE ? (const char *) recvbuf : (const char *) sendbuf;
-
-    if (regular && want_rccl(c, algorithm, elem, opidx, &nt, &no)) {
-        ncclResult_t r;
+    if (regular && want_rccl(f, algorithm, &nt, &no)) {
         /* NCCL's in-place form is recvbuff == sendbuff + rank * recvcount */
         void *dst = sendbuf == MPI_IN_PLACE ? (char *) recvbuf + (size_t) c->rank * nb : recvbuf;
-        r = rccl.ReduceScatter(src, dst, (size_t) cnts[0], nt, no, c->nccl, s);
-        if (r != ncclSuccess) {
-            MPIR_Err_set_detail("ncclReduceScatter: %s", rccl.GetErrorString ? rccl.GetErrorString(r) : "?");
-            rc = MPI_ERR_OTHER;
-            goto done;
-        }
+        ncclResult_t r = rccl.ReduceScatter(src, dst, (size_t) cnts[0], nt, no, c->nccl, s);
+        if (r != ncclSuccess)
+            return rccl_err("ncclReduceScatter", r);
         if (sendbuf == MPI_IN_PLACE && c->rank)
             HIPTRY(hipMemcpyAsync(recvbuf, dst, nb, hipMemcpyDeviceToDevice, s));
-        goto done_sync;
+        return MPI_SUCCESS;
     }
 
-    if (p > 1 && (size_t) total * esz < RSB_COMMUTATIVE_LONG_MSG_SIZE) {
-        TRY(reduce_scatter_short(c, src, recvbuf, cnts, disps, esz, opidx, elem, s, fc));
-        goto done_sync;
-    }
+    if (p > 1 && (size_t) total * esz < RSB_COMMUTATIVE_LONG_MSG_SIZE)
+        return reduce_scatter_short(f, src, recvbuf, cnts, disps);
     /* long: pairwise.  y_i = block r from rank r - i into scratch slot i-1; in
      * place, the own block is staged too when it overlaps the output. */
     slot = stage_stride(nb);
-    if (comm_scratch(c, (size_t) p * slot + 256, &scr)) {
-        MPIR_Err_set_detail("%s: scratch allocation failed", fc);
-        rc = MPI_ERR_NO_MEM;
-        goto done;
-    }
+    TRY(comm_scratch(c, (size_t) p * slot + 256, &scr, f->fc));
     ys[0] = src + (size_t) disps[c->rank] * esz;
     if (sendbuf == MPI_IN_PLACE && disps[c->rank] > 0 && disps[c->rank] < cnts[c->rank]) {
         HIPTRY(hipMemcpyAsync(scr + (size_t) (p - 1) * slot, ys[0], nb, hipMemcpyDeviceToDevice, s));
@@ -1269,74 +1228,75 @@ static int reduce_scatter_common(const char *fc, const void *sendbuf, void *recv
     }
     for (i = 1; i < p; i++) {
         int dst = (c->rank + i) % p, from = (c->rank - i + p) % p;
-        sends[i - 1].buf = (void *) (src + (size_t) disps[dst] * esz);
-        sends[i - 1].bytes = (size_t) cnts[dst] * esz;
-        sends[i - 1].peer = dst;
-        recvs[i - 1].buf = scr + (size_t) (i - 1) * slot;
-        recvs[i - 1].bytes = nb;
-        recvs[i - 1].peer = from;
+        xfer_add(sends, &nsend, src + (size_t) disps[dst] * esz, (size_t) cnts[dst] * esz, dst);
+        xfer_add(recvs, &nrecv, scr + (size_t) (i - 1) * slot, nb, from);
         ys[i] = scr + (size_t) (i - 1) * slot;
     }
-    {
-        /* large blocks: the exchange in chunks, chunk k's chain folded while
-         * k+1 moves (pipe_chunks; every rank takes the chunk count from the
-         * largest block) */
-        size_t maxb = 0, chunk = 0;
-        int nchunk;
-        for (i = 0; i < p; i++)
-            if ((size_t) cnts[i] * esz > maxb)
-                maxb = (size_t) cnts[i] * esz;
-        nchunk = p > 1 ? pipe_chunks(maxb, &chunk) : 1;
-        if (nchunk > 1) {
-            fold_ctx_t f = { ys, p, MPIR_HIP_ORDER_CHAIN, opidx, elem, recvbuf, esz, fc };
-            TRY(pipe_init(c));
-            TRY(exchange_fold_pipelined(c, sends, p - 1, recvs, p - 1, nchunk, chunk, nb, s, chunk_fold, &f));
-            HIPTRY(hipStreamWaitEvent(s, c->fev[nchunk - 1], 0));
-            goto done_sync;
-        }
+    /* large blocks: the exchange in chunks, chunk k's chain folded while
+     * k+1 moves (pipe_chunks; every rank takes the chunk count from the
+     * largest block) */
+    for (i = 0; i < p; i++)
+        if ((size_t) cnts[i] * esz > maxb)
+            maxb = (size_t) cnts[i] * esz;
+    nchunk = p > 1 ? pipe_chunks(maxb, &chunk) : 1;
+    if (nchunk > 1) {
+        fold_ctx_t fo = { ys, p, MPIR_HIP_ORDER_CHAIN, recvbuf, nb };
+        TRY(pipe_init(c));
+        TRY(exchange_fold_pipelined(f, sends, nsend, recvs, nrecv, nchunk, chunk, &fo));
+        HIPTRY(hipStreamWaitEvent(s, c->fev[nchunk - 1], 0));
+        return MPI_SUCCESS;
     }
     if (p > 1)
-        TRY(group_exchange(c, sends, p - 1, recvs, p - 1, s));
-    if (nb) {
-        rc = MPIR_Hip_combine(ys, p, recvbuf, (uint64_t) cnts[c->rank], opidx, elem, MPIR_HIP_ORDER_CHAIN, s, 0);
-        if (rc) {
-            MPIR_Op_report_hip_error(fc, rc);
-            rc = MPI_ERR_OTHER;
-            goto done;
-        }
-    }
+        TRY(group_exchange(c, sends, nsend, recvs, nrecv, s));
+    return nb ? fold_combine(f, ys, p, recvbuf, cnts[c->rank], MPIR_HIP_ORDER_CHAIN, s) : MPI_SUCCESS;
+}
 
-  done_sync:
-    if (rc == MPI_SUCCESS && !hip_stream)
-        HIPTRY(hipStreamSynchronize(s));
-  done:
-    if (cur != c->device)
-        (void) hipSetDevice(cur);
-    return rc ? MPIR_Err_return(fc, rc) : MPI_SUCCESS;
+/* f: fc and c set by the entry point */
+static int reduce_scatter_common(coll_t *f, const void *sendbuf, void *recvbuf, const int *counts,
+                                 MPI_Datatype datatype, MPI_Op op, int algorithm, void *hip_stream)
+{
+    int rc, i, regular = 1;
+    long cnts[MAX_RANKS] = {0}, disps[MAX_RANKS] = {0}, total = 0;
+
+    if (!f->c) {
+        MPIR_Err_set_detail("%s: null communicator", f->fc);
+        return MPIR_Err_return(f->fc, MPI_ERR_ARG);
+    }
+    for (i = 0; i < f->c->size; i++) {
+        if (counts[i] < 0) {
+            MPIR_Err_set_detail("%s: negative count", f->fc);
+            return MPIR_Err_return(f->fc, MPI_ERR_COUNT);
+        }
+        cnts[i] = counts[i];
+        disps[i] = total;
+        total += counts[i];
+        regular &= counts[i] == counts[0];
+    }
+    /* op / type validation; the alias check applies when any data moves */
+    if (!coll_begin(f, sendbuf, recvbuf, total > 0, datatype, op, hip_stream, &rc))
+        return rc;
+    return coll_end(f, reduce_scatter_schedule(f, sendbuf, recvbuf, cnts, disps, regular, algorithm));
 }
 
 int MPIX_Reduce_scatter_block_hip(const void *sendbuf, void *recvbuf, int recvcount, MPI_Datatype datatype,
                                   MPI_Op op, MPIX_Hip_comm comm, int algorithm, void *hip_stream)
 {
-    int counts[64], i;
-    if (!comm || recvcount < 0)
-        return reduce_scatter_common("MPIX_Reduce_scatter_block_hip", sendbuf, recvbuf,
-                                     (int[64]) { recvcount }, datatype, op, comm, algorithm, hip_stream);
-    for (i = 0; i < comm->size; i++)
+    coll_t f = { .fc = "MPIX_Reduce_scatter_block_hip", .c = comm };
+    int counts[MAX_RANKS] = { recvcount }, i;
+    for (i = 0; comm && recvcount >= 0 && i < comm->size; i++)
         counts[i] = recvcount;
-    return reduce_scatter_common("MPIX_Reduce_scatter_block_hip", sendbuf, recvbuf, counts, datatype, op, comm,
-                                 algorithm, hip_stream);
+    return reduce_scatter_common(&f, sendbuf, recvbuf, counts, datatype, op, algorithm, hip_stream);
 }
 
 int MPIX_Reduce_scatter_hip(const void *sendbuf, void *recvbuf, const int recvcounts[], MPI_Datatype datatype,
                             MPI_Op op, MPIX_Hip_comm comm, int algorithm, void *hip_stream)
 {
+    coll_t f = { .fc = "MPIX_Reduce_scatter_hip", .c = comm };
     if (!recvcounts) {
         MPIR_Err_set_detail("MPIX_Reduce_scatter_hip: recvcounts is NULL");
-        return MPIR_Err_return("MPIX_Reduce_scatter_hip", MPI_ERR_ARG);
+        return MPIR_Err_return(f.fc, MPI_ERR_ARG);
     }
-    return reduce_scatter_common("MPIX_Reduce_scatter_hip", sendbuf, recvbuf, recvcounts, datatype, op, comm,
-                                 algorithm, hip_stream);
+    return reduce_scatter_common(&f, sendbuf, recvbuf, recvcounts, datatype, op, algorithm, hip_stream);
 }
 
 /* ------------------------------------------------------------ Scan / Exscan
@@ -1353,103 +1313,73 @@ int MPIX_Reduce_scatter_hip(const void *sendbuf, void *recvbuf, const int recvco
  * sends its vector to all higher ranks in ONE exchange (all xGMI links at
  * once instead of log2(p) dependent rounds), then folds the trees and the
  * chain on the device.  RCCL has no scan; MPIX_HIP_ALG_RCCL runs this too. */
-static int scan_common(const char *fc, const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype,
-                       MPI_Op op, MPIX_Hip_comm comm, void *hip_stream, int exclusive)
+static int scan_schedule(const coll_t *f, const void *sendbuf, void *recvbuf, int count, int exclusive)
 {
-    struct MPIX_Hip_comm_s *c = comm;
-    int elem = 0, opidx = op & 0xf, rc, p, r, q, m, nx = 0, nr = 0, nparts = 0, cur = 0;
-    size_t esz, bytes, slot;
-    hipStream_t s;
+    struct MPIX_Hip_comm_s *c = f->c;
+    const void *own = sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf;
+    int p = c->size, r = c->rank, q, m, nsend = 0, nrecv = 0, nchain = 0, nparts = 0;
+    size_t bytes = (size_t) count * f->esz, slot = stage_stride(bytes);
     xfer_t sends[MAX_XFER], recvs[MAX_XFER];
-    const void *chain[64], *ys[64];
-    const void *own;
+    const void *chain[MAX_RANKS], *ys[MAX_RANKS];
     char *scr = NULL;
 
-    if (!comm) {
-        MPIR_Err_set_detail("%s: null communicator", fc);
-        return MPIR_Err_return(fc, MPI_ERR_ARG);
-    }
-    /* the exscan's recvbuf is not significant at rank 0 */
-    rc = coll_check(fc, sendbuf, (exclusive && comm->rank == 0 && sendbuf != MPI_IN_PLACE) ? NULL : recvbuf, count,
-                    datatype, op, comm, &elem);
-    if (rc)
-        return MPIR_Err_return(fc, rc);
-    if (count == 0)
-        return MPI_SUCCESS;
-    if (hipGetDevice(&cur) == hipSuccess && cur != c->device)
-        (void) hipSetDevice(c->device);
-    s = hip_stream ? (hipStream_t) hip_stream : c->stream;
-    esz = MPIR_Hip_elem_size(elem);
-    bytes = (size_t) count * esz;
-    slot = stage_stride(bytes);
-    p = c->size;
-    r = c->rank;
-    own = sendbuf == MPI_IN_PLACE ? recvbuf : sendbuf;
     for (m = 1; m <= r; m <<= 1)
         nparts += (r & m) != 0;
-    if (p > 1 && comm_scratch(c, (size_t) (r + nparts + 1) * slot, &scr)) {
-        MPIR_Err_set_detail("%s: scratch allocation failed", fc);
-        rc = MPI_ERR_NO_MEM;
-        goto done;
-    }
+    if (p > 1)
+        TRY(comm_scratch(c, (size_t) (r + nparts + 1) * slot, &scr, f->fc));
     /* every rank's vector to all higher ranks; x_q lands in slot q */
     for (q = 0; q < p; q++) {
-        if (q > r) {
-            sends[nx].buf = (void *) own;
-            sends[nx].bytes = bytes;
-            sends[nx++].peer = q;
-        } else if (q < r) {
-            recvs[nr].buf = scr + (size_t) q * slot;
-            recvs[nr].bytes = bytes;
-            recvs[nr++].peer = q;
-        }
+        if (q > r)
+            xfer_add(sends, &nsend, own, bytes, q);
+        else if (q < r)
+            xfer_add(recvs, &nrecv, scr + (size_t) q * slot, bytes, q);
     }
     if (p > 1)
-        TRY(group_exchange(c, sends, nx, recvs, nr, s));
-    nx = 0;
+        TRY(group_exchange(c, sends, nsend, recvs, nrecv, f->s));
     if (!exclusive)
-        chain[nx++] = own;
+        chain[nchain++] = own;
     for (m = 1, q = 0; m <= r; m <<= 1) {
         int d, j;
         if (!(r & m))
             continue;
         d = r ^ m;
         if (m == 1) {
-            chain[nx++] = scr + (size_t) d * slot;
+            chain[nchain++] = scr + (size_t) d * slot;
         } else {
             char *t = scr + (size_t) (r + q++) * slot;
             for (j = 0; j < m; j++)
                 ys[j] = scr + (size_t) (d ^ j) * slot;
-            TRY(fold_tree(ys, m, t, count, opidx, elem, s, fc));
-            chain[nx++] = t;
+            TRY(fold_tree(f, ys, m, t, count));
+            chain[nchain++] = t;
         }
     }
-    if (nx > 0) {
-        rc = MPIR_Hip_combine(chain, nx, recvbuf, (uint64_t) count, opidx, elem, MPIR_HIP_ORDER_CHAIN, s, 0);
-        if (rc) {
-            MPIR_Op_report_hip_error(fc, rc);
-            rc = MPI_ERR_OTHER;
-            goto done;
-        }
-    }
-    if (!hip_stream)
-        HIPTRY(hipStreamSynchronize(s));
-  done:
-    if (cur != c->device)
-        (void) hipSetDevice(cur);
-    return rc ? MPIR_Err_return(fc, rc) : MPI_SUCCESS;
+    return nchain ? fold_combine(f, chain, nchain, recvbuf, count, MPIR_HIP_ORDER_CHAIN, f->s) : MPI_SUCCESS;
+}
+
+/* f: fc and c set by the entry point */
+static int scan_common(coll_t *f, const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype, MPI_Op op,
+                       void *hip_stream, int exclusive)
+{
+    int rc;
+    /* the exscan's recvbuf is not significant at rank 0 */
+    if (!coll_begin(f, sendbuf, (exclusive && f->c && f->c->rank == 0 && sendbuf != MPI_IN_PLACE) ? NULL : recvbuf,
+                    count, datatype, op, hip_stream, &rc))
+        return rc;
+    return coll_end(f, scan_schedule(f, sendbuf, recvbuf, count, exclusive));
 }
 
 int MPIX_Scan_hip(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype, MPI_Op op,
                   MPIX_Hip_comm comm, int algorithm, void *hip_stream)
 {
+    coll_t f = { .fc = "MPIX_Scan_hip", .c = comm };
     (void) algorithm;
-    return scan_common("MPIX_Scan_hip", sendbuf, recvbuf, count, datatype, op, comm, hip_stream, 0);
+    return scan_common(&f, sendbuf, recvbuf, count, datatype, op, hip_stream, 0);
 }
 
 int MPIX_Exscan_hip(const void *sendbuf, void *recvbuf, int count, MPI_Datatype datatype, MPI_Op op,
                     MPIX_Hip_comm comm, int algorithm, void *hip_stream)
 {
+    coll_t f = { .fc = "MPIX_Exscan_hip", .c = comm };
     (void) algorithm;
-    return scan_common("MPIX_Exscan_hip", sendbuf, recvbuf, count, datatype, op, comm, hip_stream, 1);
+    return scan_common(&f, sendbuf, recvbuf, count, datatype, op, hip_stream, 1);
 }

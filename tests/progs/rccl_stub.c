@@ -11,7 +11,12 @@
  *         allreduce <count> <type> <op> | reduce_scatter <recvcount> <type> <op>
  *         reduce <count> <type> <op> <root> | destroy
  *         note <text>                       (from the harness: memcpy, combine, ...)
+ *         note + <call> <name>=<value> ...  (the buffers and the stream of the
+ *                                           call on the line before, by the
+ *                                           names tests/progs/coll_trace.c gives them)
  */
+#define _GNU_SOURCE
+#include <dlfcn.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -44,6 +49,27 @@ void rccl_stub_note(const char *text)
     out("note %s", text);
 }
 
+/* the buffers and the stream of the call just logged, by the harness's names
+ * (its lookup functions, found the way its note() finds rccl_stub_note) */
+typedef const char *(*name_fn)(const void *, char *, size_t);
+
+static void detail(const char *call, const void *sb, const void *rb, int has_rb, hipStream_t s)
+{
+    static name_fn ptr_name, stream_name;
+    char a[64], b[64], c[32];
+    if (!ptr_name) {
+        *(void **) (&ptr_name) = dlsym(RTLD_DEFAULT, "coll_trace_ptr_name");
+        *(void **) (&stream_name) = dlsym(RTLD_DEFAULT, "coll_trace_stream_name");
+    }
+    if (!ptr_name || !stream_name)
+        return;
+    if (has_rb)
+        out("note + %s sendbuf=%s recvbuf=%s stream=%s", call, ptr_name(sb, a, sizeof a), ptr_name(rb, b, sizeof b),
+            stream_name((const void *) s, c, sizeof c));
+    else
+        out("note + %s buf=%s stream=%s", call, ptr_name(sb, a, sizeof a), stream_name((const void *) s, c, sizeof c));
+}
+
 ncclResult_t ncclGetUniqueId(ncclUniqueId *id)
 {
     memset(id, 0, sizeof(*id));
@@ -71,6 +97,10 @@ ncclResult_t ncclCommInitRank(ncclComm_t *comm, int nranks, ncclUniqueId id, int
 ncclResult_t ncclCommDestroy(ncclComm_t comm)
 {
     out("destroy");
+    /* the last line of a log: what the harness notes while the rest of the
+     * communicator is torn down is not recorded */
+    fclose(logf_);
+    logf_ = NULL;
     free(comm);
     return ncclSuccess;
 }
@@ -93,55 +123,47 @@ ncclResult_t ncclGroupEnd(void)
 
 ncclResult_t ncclSend(const void *buf, size_t count, ncclDataType_t t, int peer, ncclComm_t comm, hipStream_t s)
 {
-    (void) buf;
-    (void) s;
     if (peer < 0 || peer >= comm->nranks || peer == comm->rank)
         return ncclInvalidArgument;
     out("send %zu %d %d", count, (int) t, peer);
+    detail("send", buf, NULL, 0, s);
     return ncclSuccess;
 }
 
 ncclResult_t ncclRecv(void *buf, size_t count, ncclDataType_t t, int peer, ncclComm_t comm, hipStream_t s)
 {
-    (void) buf;
-    (void) s;
     if (peer < 0 || peer >= comm->nranks || peer == comm->rank)
         return ncclInvalidArgument;
     out("recv %zu %d %d", count, (int) t, peer);
+    detail("recv", buf, NULL, 0, s);
     return ncclSuccess;
 }
 
 ncclResult_t ncclAllReduce(const void *sb, void *rb, size_t count, ncclDataType_t t, ncclRedOp_t op,
                            ncclComm_t comm, hipStream_t s)
 {
-    (void) sb;
-    (void) rb;
     (void) comm;
-    (void) s;
     out("allreduce %zu %d %d", count, (int) t, (int) op);
+    detail("allreduce", sb, rb, 1, s);
     return ncclSuccess;
 }
 
 ncclResult_t ncclReduceScatter(const void *sb, void *rb, size_t recvcount, ncclDataType_t t, ncclRedOp_t op,
                                ncclComm_t comm, hipStream_t s)
 {
-    (void) sb;
-    (void) rb;
     (void) comm;
-    (void) s;
     out("reduce_scatter %zu %d %d", recvcount, (int) t, (int) op);
+    detail("reduce_scatter", sb, rb, 1, s);
     return ncclSuccess;
 }
 
 ncclResult_t ncclReduce(const void *sb, void *rb, size_t count, ncclDataType_t t, ncclRedOp_t op, int root,
                         ncclComm_t comm, hipStream_t s)
 {
-    (void) sb;
-    (void) rb;
-    (void) s;
     if (root < 0 || root >= comm->nranks)
         return ncclInvalidArgument;
     out("reduce %zu %d %d %d", count, (int) t, (int) op, root);
+    detail("reduce", sb, rb, 1, s);
     return ncclSuccess;
 }
 
