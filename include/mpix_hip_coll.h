@@ -29,6 +29,10 @@
  *
  * Streams: stream == NULL runs on the communicator's stream and returns with
  * the result complete; otherwise the collective is enqueued on that stream.
+ * Between two consecutive calls of a communicator on different streams the
+ * caller has completed the earlier one (the communicator's staging scratch
+ * and events are reused by every call; calls on one stream may follow one
+ * another with no synchronisation).
  */
 #ifndef MPIX_HIP_COLL_H_INCLUDED
 #define MPIX_HIP_COLL_H_INCLUDED

@@ -8,10 +8,14 @@ only in its transport (grouped ncclSend/ncclRecv) and needs one GPU per rank.
 Expected bytes: oracle/schedules.py, the reference schedules run step by step
 on the CPU oracle.  Bit-exact (complex NaN payloads excepted).
 
-Not tested here: two pipelined collectives back to back on a caller's stream
-(ADVICE.md round 6).  The loopback transport synchronises the stream after
-every group, so on one GPU that case passes whether or not the ordering
-across the two calls is right; it needs the RCCL transport.
+Two pipelined collectives back to back on a caller's stream (ADVICE.md round
+6) are not decided here: the loopback transport synchronises the stream after
+every group, so on one GPU that case passes whether or not the ordering across
+the two calls is right.  tests/test_coll_order_cpu.py decides it without a GPU,
+from the happens-before order of the logged HIP and RCCL calls;
+tests/test_coll_stream_gpu.py runs the collectives on a caller's stream over
+this transport, and tests/test_coll_rccl_gpu.py runs the back-to-back pair over
+RCCL where more than one GPU is visible.
 """
 import threading
 

@@ -285,3 +285,119 @@ def test_config_size_collectives_over_rccl(mpi, cuda, size, alg):
         assert res[r][1] == "ok", res[r]
         for name, (rc, ok) in res[r][3].items():
             assert rc == 0 and ok, (name, alg, r)
+
+
+# ---------------------------------------------------------------------------
+# On a caller's stream (a non-NULL hip_stream): nothing synchronises with the
+# host, so two calls in a row overlap, and over RCCL -- unlike the loopback
+# transport, which synchronises inside every exchange -- a missing wait between
+# them would show.  tests/test_coll_order_cpu.py proves the ordering from the
+# logged call sequence; this runs it.
+# ---------------------------------------------------------------------------
+STREAM_N = (1 << 19) + 7
+
+
+def _stream_rank_main(rank, size, uid, q, algs):
+    """One rank: on one stream of its own, behind slow work and the copy that
+    brings the input, an Allreduce fp32 SUM of STREAM_N and, with nothing in
+    between, a Reduce_scatter_block whose sendbuf is the Allreduce's recvbuf
+    (recvcount STREAM_N // size); a stream-ordered copy out; that stream alone
+    is synchronised.  Once per algorithm of `algs`."""
+    os.environ["MPIR_CVAR_DEVICE_COLL_PIPELINE_KB"] = "64"
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "mpich-pip_amd"))
+    sys.path.insert(0, ROOT)
+    import ctypes
+    import torch
+    import mpich_pip_amd as mpi
+    torch.cuda.set_device(rank)
+    lib = mpi.load()
+    lib.MPIX_Reduce_local_set_errhandler(mpi.MPI_ERRORS_RETURN)
+    comm = ctypes.c_void_p()
+    rc = lib.MPIX_Hip_comm_create(ctypes.c_char_p(uid), size, rank, ctypes.byref(comm))
+    if rc:
+        q.put((rank, "create", rc, mpi.error_string(rc)))
+        return
+    n, rcnt = STREAM_N, STREAM_N // size
+    x = np.random.default_rng(2000 + rank).uniform(-1, 1, n).astype(np.float32)
+    hin = torch.from_numpy(x).pin_memory()
+    big = torch.ones(64 << 20, device="cuda")
+    out = []
+    for alg in algs:
+        send = torch.full((n,), float("nan"), device="cuda")
+        mid = torch.full((n,), float("nan"), device="cuda")
+        recv = torch.full((rcnt + 16,), float("nan"), device="cuda")
+        hmid = torch.zeros(n).pin_memory()
+        hout = torch.zeros(rcnt + 16).pin_memory()
+        st = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(st):
+            for _ in range(20):
+                big.mul_(1.0000001)
+            send.copy_(hin, non_blocking=True)
+            rc1 = mpi.allreduce(send.data_ptr(), mid.data_ptr(), n, mpi.MPI_FLOAT, mpi.MPI_SUM, comm.value, alg,
+                                st.cuda_stream)
+            rc2 = mpi.reduce_scatter_block(mid.data_ptr(), recv.data_ptr(), rcnt, mpi.MPI_FLOAT, mpi.MPI_SUM,
+                                           comm.value, alg, st.cuda_stream)
+            hmid.copy_(mid, non_blocking=True)
+            hout.copy_(recv, non_blocking=True)
+        st.synchronize()
+        out.append((rc1, rc2, x.view(np.uint8), hmid.numpy().view(np.uint8).copy(), hout.numpy().view(np.uint8).copy()))
+    q.put((rank, "ok", 0, out))
+    torch.cuda.synchronize()
+    mpi.comm_free(comm.value)
+
+
+def _run_stream(size, algs):
+    import ctypes
+    import mpich_pip_amd as mpi
+    uid = ctypes.create_string_buffer(128)
+    assert mpi.load().MPIX_Hip_comm_get_unique_id(uid) == 0
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    procs = [ctx.Process(target=_stream_rank_main, args=(r, size, uid.raw, q, algs)) for r in range(size)]
+    for p in procs:
+        p.start()
+    res = {}
+    for _ in range(size):
+        r = q.get(timeout=300)
+        res[r[0]] = r
+    for p in procs:
+        p.join(60)
+    for r in range(size):
+        assert res[r][1] == "ok", res[r]
+    return res
+
+
+@pytest.mark.parametrize("size", [2, 8])
+def test_back_to_back_on_a_callers_stream_over_rccl(mpi, orc, cuda, size):
+    """Two pipelined reference-order collectives in a row on one caller's
+    stream per rank, the second reading what the first wrote, over the RCCL
+    transport: bit-exact against the oracle's schedules composed."""
+    from oracle import schedules as S
+    if _ngpus() < size:
+        pytest.skip(f"needs {size} GPUs, {_ngpus()} visible")
+    res = _run_stream(size, [mpi.MPIX_HIP_ALG_REFERENCE_ORDER])
+    n, rcnt = STREAM_N, STREAM_N // size
+    xs = [res[r][3][0][2] for r in range(size)]
+    mid = S.allreduce_smp_auto(xs, n, 4, mpi.MPI_FLOAT, mpi.MPI_SUM)
+    want = S.reduce_scatter_block_auto([mid[:size * rcnt * 4].copy() for _ in range(size)], rcnt, 4, mpi.MPI_FLOAT,
+                                       mpi.MPI_SUM)
+    for r in range(size):
+        rc1, rc2, _, gmid, gout = res[r][3][0]
+        assert rc1 == 0 and rc2 == 0, (r, rc1, rc2)
+        assert np.array_equal(gmid, mid), f"rank {r}: allreduce: {np.count_nonzero(gmid != mid)} bytes differ"
+        assert np.array_equal(gout[:rcnt * 4], want[r]), f"rank {r}: {np.count_nonzero(gout[:rcnt * 4] != want[r])}"
+        assert np.isnan(gout[rcnt * 4:].view(np.float32)).all(), f"rank {r}: wrote behind recvbuf"
+
+
+def test_one_rank_rccl_on_a_callers_stream(mpi, cuda):
+    """A 1-rank RCCL communicator (always runs): ncclAllReduce and
+    ncclReduceScatter on the caller's stream, MPIX_HIP_ALG_RCCL and AUTO, behind
+    slow work and the input's copy on that stream; the result is the input."""
+    res = _run_stream(1, [mpi.MPIX_HIP_ALG_RCCL, mpi.MPIX_HIP_ALG_AUTO])
+    for k, (rc1, rc2, x, gmid, gout) in enumerate(res[0][3]):
+        assert rc1 == 0 and rc2 == 0, (k, rc1, rc2)
+        assert np.array_equal(gmid, x), f"alg {k}: allreduce: {np.count_nonzero(gmid != x)} bytes differ"
+        assert np.array_equal(gout[:STREAM_N * 4], x), f"alg {k}: reduce_scatter_block differs"
+        assert np.isnan(gout[STREAM_N * 4:].view(np.float32)).all(), f"alg {k}: wrote behind recvbuf"

@@ -566,3 +566,88 @@ def test_fold_grid_stride_loops_take_another_stride(mpi, orc, cuda, op, t, order
     want = _fold(orc, xs, count, dt, o, order)
     want_path = {"elements": mpi.COMBINE_FUSED_ELEMENTS, "vector": mpi.COMBINE_FUSED_VECTOR, "any": mpi.COMBINE_ANY}[path]
     _run_fold(mpi, torch, xs, want, t, op, order, [off] + [0] * (n - 1), 0, want_path)
+
+
+# ---------------------------------------------------------------------------
+# MPIX_Reduce_local_multi on a caller's stream (stream=): the fold is enqueued
+# and not waited for, so its operands may still be arriving on that stream and
+# its result is complete only in that stream's order.  The device collectives
+# launch every fold this way (csrc/host/coll_hip.c fold_combine).
+# ---------------------------------------------------------------------------
+STREAM_FOLDS = [("MPI_SUM", "MPI_FLOAT", "TREE", 4, [4, 4, 4, 4], 4, False, "vector"),       # one element past 16 B
+                ("MPI_SUM", "MPI_FLOAT", "TREE", 4, [0, 0, 4, 0], 0, False, "elements"),     # one operand 4 B off
+                ("MPI_MINLOC", "MPI_2INT", "TREE", 16, [0] * 16, 0, False, "any"),
+                ("MPI_SUM", "MPIX_C_FLOAT16", "CHAIN", 11, [0] * 11, 0, True, "vector")]     # two passes, out == in[0]
+
+
+def _fold_on_stream(mpi, torch, big, xs, t, op, order, offs, off_out, alias):
+    """The fold with every operand's payload 0xA5 until a copy queued on the
+    caller's stream -- behind slow work -- brings the data; the fold and the
+    copy of the whole output allocation to pinned memory follow on that stream,
+    which alone is synchronised.  Returns the output allocation's bytes."""
+    esz = T.elem_size(t)
+    nb = xs[0].size
+    dev, pinned = [], [torch.from_numpy(x.copy()).pin_memory() for x in xs]
+    for off in offs:
+        d = torch.zeros(nb + off + 64, dtype=torch.uint8, device="cuda")
+        d[off:off + nb] = 0xA5
+        dev.append(d)
+    out = dev[0] if alias else torch.zeros(nb + off_out + 64, dtype=torch.uint8, device="cuda")
+    host = torch.zeros(out.numel(), dtype=torch.uint8).pin_memory()
+    st = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(st):
+        for _ in range(20):                 # as test_pinned_host_operand_ordered_after_null_stream
+            big.mul_(1.0000001)
+        for d, off, h in zip(dev, offs, pinned):
+            d[off:off + nb].copy_(h, non_blocking=True)
+        rc = mpi.reduce_local_multi([d.data_ptr() + off for d, off in zip(dev, offs)], out.data_ptr() + off_out,
+                                    nb // esz, mpi.DATATYPES[t], mpi.OPS[op],
+                                    mpi.MPIX_ORDER_TREE if order == "TREE" else mpi.MPIX_ORDER_CHAIN,
+                                    stream=st.cuda_stream)
+        assert rc == 0, mpi.error_string(rc)
+        host.copy_(out, non_blocking=True)
+    st.synchronize()
+    return host.numpy().copy()
+
+
+@pytest.mark.parametrize("op,t,order,n,offs,off_out,alias,path", STREAM_FOLDS,
+                         ids=[f"{o}-{t}-{r}{n}-{p}" for o, t, r, n, _, _, _, p in STREAM_FOLDS])
+def test_fold_on_a_callers_stream(mpi, orc, cuda, op, t, order, n, offs, off_out, alias, path):
+    """The fused vector kernel, the fused element kernel, k_combine_any and a
+    two-pass CHAIN into its own first operand with stream=: the operands are
+    poison until the caller's stream delivers them, the result is read in that
+    stream's order only (no null-stream operation in between).  Then the same
+    under MPIR_Hip_combine_set_flags(MPIR_HIP_COMBINE_UNCAPPED): the same bytes,
+    and the call returns the flags it replaced."""
+    torch = cuda
+    esz = T.elem_size(t)
+    dt, o = mpi.DATATYPES[t], mpi.OPS[op]
+    count = 4099 + 3
+    nb = count * esz
+    rng = np.random.default_rng(n + count)
+    xs = [T.to_bytes(T.gen(t, count, rng, op)) for _ in range(n)]
+    want = _fold(orc, xs, count, dt, o, order)
+    want_path = {"elements": mpi.COMBINE_FUSED_ELEMENTS, "vector": mpi.COMBINE_FUSED_VECTOR, "any": mpi.COMBINE_ANY}[path]
+    a = 1 << 32                                     # (made-up 16 B-aligned addresses: never dereferenced)
+    info = mpi.combine_plan_info([a + (j << 24) + off for j, off in enumerate(offs)],
+                                 a + off_out + (0 if alias else 64 << 24), count, dt, o,
+                                 mpi.MPIX_ORDER_TREE if order == "TREE" else mpi.MPIX_ORDER_CHAIN)
+    assert info["path"] == want_path and info["passes"] == (2 if n == 11 else 1), info
+    big = torch.ones(64 << 20, device="cuda")
+    lib = mpi.load()
+    UNCAPPED = 1                                    # MPIR_HIP_COMBINE_UNCAPPED (include/mpir_hip_reduce.h)
+    runs = {}
+    for flags in (0, UNCAPPED):
+        prev = lib.MPIR_Hip_combine_set_flags(flags)
+        try:
+            assert prev == 0, "the thread's combine flags were left set"
+            whole = _fold_on_stream(mpi, torch, big, xs, t, op, order, offs, off_out, alias)
+        finally:
+            assert lib.MPIR_Hip_combine_set_flags(prev) == flags        # round trip: what was set comes back
+        assert lib.MPIR_Hip_combine_set_flags(0) == prev
+        got = whole[off_out:off_out + nb]
+        assert same(got, want, t), f"flags={flags}: {np.count_nonzero(got != want)} bytes differ"
+        assert not whole[:off_out].any() and not whole[off_out + nb:].any(), f"flags={flags}: wrote outside the output"
+        runs[flags] = whole
+    assert np.array_equal(runs[0], runs[UNCAPPED]), "uncapped fold differs from the capped one"
