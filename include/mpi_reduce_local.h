@@ -268,6 +268,42 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_multi(const void *const *inbufs, int n, v
 typedef struct MPIX_Reduce_local_seg { const void *inbuf; void *inoutbuf; int count; } MPIX_Reduce_local_seg;
 MPICH_API_PUBLIC int MPIX_Reduce_local_batch(const MPIX_Reduce_local_seg *segs, int nsegs,
                             MPI_Datatype datatype, MPI_Op op, void *hip_stream);
+/* Strided local reduction: the rows of a vector-shaped operand in one launch --
+ * the target of an accumulate on an MPI_Type_vector / hvector type, a
+ * sub-matrix, a halo face, a column.  For r in [0, nblocks):
+ *   MPI_Reduce_local((char *) inbuf + r * in_stride, (char *) inoutbuf + r * inout_stride,
+ *                    blocklen, datatype, op)
+ * every row bit-identical to that call; the bytes between rows are never read
+ * or written.  Strides are in bytes (MPI_Type_create_hvector's unit).
+ *   hip_stream NULL: synchronous on the calling thread's library stream, every
+ *       row complete on return; otherwise enqueued on that stream without
+ *       waiting.  The launch carries the five numbers that describe the operands
+ *       in its kernel arguments: nothing of the caller's is read afterwards.
+ *   Builtin ops and basic types, validated as the batch validates a segment
+ *       (MPI_REPLACE, MPI_NO_OP, null and invalid ops: MPI_ERR_OP; inbuf ==
+ *       inoutbuf: MPI_ERR_BUFFER under MPIR_CVAR_COLL_ALIAS_CHECK; MPI_IN_PLACE:
+ *       MPI_ERR_BUFFER); user ops give MPI_ERR_OP (they run on the host),
+ *       MPI_LAND / MPI_LOR on floating types MPI_ERR_OP.
+ *   nblocks < 0 or blocklen < 0 is MPI_ERR_COUNT.  Either one 0 succeeds, and
+ *       the pointers are not looked at.
+ *   A negative stride is MPI_ERR_ARG.  With nblocks > 1, inout_stride below the
+ *       row's bytes (blocklen x the datatype's size) is MPI_ERR_ARG: output rows
+ *       would overlap.  in_stride may be anything >= 0; 0 combines the same
+ *       input row into every output row.
+ *   The first and the last byte of each operand's span must be device memory,
+ *       all on one device (else MPI_ERR_BUFFER); what lies between is the
+ *       caller's, as with any MPI buffer.  Host operands are not taken (the
+ *       batch refuses them too): MPI_Reduce_local row by row serves them.
+ *   Everything is validated and classified before the first launch: a call
+ *       that returns an error has modified nothing.
+ *   An input span overlapping the output span is undefined (not checked, but
+ *       for inbuf == inoutbuf above): the rows run concurrently.
+ *   nblocks == 1, or both strides equal to the row's bytes (contiguous rows),
+ *       is the single call on nblocks x blocklen elements.
+ * Ragged rows, or rows at irregular places, are MPIX_Reduce_local_batch's. */
+MPICH_API_PUBLIC int MPIX_Reduce_local_strided(const void *inbuf, MPI_Aint in_stride,
+                              void *inoutbuf, MPI_Aint inout_stride, int nblocks, int blocklen,
+                              MPI_Datatype datatype, MPI_Op op, void *hip_stream);
 MPICH_API_PUBLIC int MPIX_Reduce_local_set_errhandler(MPI_Errhandler errhandler);
 MPICH_API_PUBLIC int MPIX_Reduce_local_get_errhandler(MPI_Errhandler * errhandler);
 

@@ -56,6 +56,7 @@ enum MPIR_Hip_elem {
 #define MPIR_HIP_ERUNTIME  2   /* HIP runtime failure; see MPIR_Hip_error_string() */
 #define MPIR_HIP_ENOKERNEL 3   /* (op, elem) pair has no kernel */
 #define MPIR_HIP_ENODEV    4   /* no usable GPU */
+#define MPIR_HIP_EARG      5   /* an argument out of range (MPIR_Hip_reduce_strided's strides) */
 
 /* Combine inoutbuf[i] = op(inoutbuf[i], inbuf[i]) for i < count elements of
  * class `elem`.  Pointers may be device, pinned-host or pageable-host memory
@@ -142,6 +143,54 @@ int MPIR_Hip_reduce_batch(const MPIR_Hip_seg *segs, int nsegs, int op, int elem,
 #define MPIR_HIP_BATCH_MAX_GROUPS (1ull << 23)
 int MPIR_Hip_batch_plan_info(const MPIR_Hip_seg *segs, int nsegs, int op, int elem,
                              uint64_t out[6], uint32_t *seg_kind, uint32_t *seg_groups);
+
+/* Strided reduction: for r < nblocks, io_r[i] = op(io_r[i], in_r[i]), i <
+ * blocklen, where in_r = inbuf + r * in_stride and io_r = inoutbuf + r *
+ * io_stride (strides in bytes) -- the rows of an MPI_Type_vector operand under
+ * one (op, elem), in one kernel launch however many rows there are (further
+ * launches on the same stream take later row ranges once a launch would pass
+ * MPIR_HIP_BATCH_MAX_GROUPS workgroups).  Each row's result is bit-identical to
+ * MPIR_Hip_reduce on it; bytes between rows are never read or written.
+ * nblocks == 0 or blocklen == 0 succeeds with no pointer looked at.  With
+ * nblocks > 1, io_stride below the row's bytes (output rows would overlap), or
+ * a span past the end of the address space, is MPIR_HIP_EARG; in_stride may be
+ * anything, 0 combines one input row into every output row.  The first and the
+ * last byte of each operand's span must be device memory, all on one device
+ * (else MPIR_HIP_EBUFFER); they are classified before the first launch, so a
+ * call that fails has written nothing.  nblocks == 1, or both strides equal to
+ * the row's bytes, is MPIR_Hip_reduce on nblocks * blocklen elements.
+ * hip_stream / sync as for MPIR_Hip_reduce; the launch carries everything in
+ * its kernel arguments.  MPIR_HIP_ENOKERNEL for REPLACE and pairs with no kernel. */
+int MPIR_Hip_reduce_strided(const void *inbuf, uint64_t in_stride, void *inoutbuf, uint64_t io_stride,
+                            uint64_t nblocks, uint64_t blocklen, int op, int elem, void *hip_stream, int sync);
+
+/* For tests and tools: the launches MPIR_Hip_reduce_strided would make for
+ * device operands at these addresses, from the same planner the launch calls
+ * (host arithmetic on the pointer values only).  out = {form, launches,
+ * workgroups over all launches, G (WIDE: workgroups per row) or units per
+ * workgroup (NARROW), rows on the tile path, rows on the element path (both
+ * WIDE only, else 0), the wide / narrow threshold in force (bytes), rows per
+ * launch}.  SINGLE reports MPIR_Hip_plan_info's grid as its workgroups.
+ * Returns as MPIR_Hip_reduce_strided does for the same arguments, residency
+ * apart. */
+#define MPIR_HIP_STRIDED_EMPTY        0   /* nblocks or blocklen 0: nothing to do */
+#define MPIR_HIP_STRIDED_SINGLE       1   /* one row, or contiguous rows: MPIR_Hip_reduce's own plan */
+#define MPIR_HIP_STRIDED_WIDE         2   /* row bytes >= the threshold: nblocks x G workgroups, the batch's segment code */
+#define MPIR_HIP_STRIDED_NARROW_VEC   3   /* flattened 16-byte units: row bytes, strides and bases all multiples of 16 */
+#define MPIR_HIP_STRIDED_NARROW_ELEMS 4   /* flattened elements, any alignment */
+int MPIR_Hip_strided_plan_info(const void *inbuf, uint64_t in_stride, const void *inoutbuf, uint64_t io_stride,
+                               uint64_t nblocks, uint64_t blocklen, int op, int elem, uint64_t out[8]);
+/* Rows of at least this many bytes take the WIDE form
+ * (MPIR_CVAR_REDUCE_LOCAL_STRIDED_WIDE_KB, default 16 KiB; 0: every row; at most
+ * 1 GiB).  The setter changes it at run time (tools/strided_ab.py forces each
+ * form with it) and returns the previous value. */
+uint64_t MPIR_Hip_set_strided_wide_bytes(uint64_t bytes);
+/* Test hook: the calling thread's strided launches close before `groups`
+ * workgroups instead of MPIR_HIP_BATCH_MAX_GROUPS (never inside a row of the
+ * WIDE form), so that the row-range split runs at a small size
+ * (tests/test_strided_gpu.py).  0, or more than the real cap: the real cap.
+ * Returns the previous value. */
+uint64_t MPIR_Hip_strided_test_max_groups(uint64_t groups);
 
 /* Flags for the calling thread's later MPIR_Hip_combine calls; returns the
  * previous flags.  MPIR_HIP_COMBINE_UNCAPPED: the fused folds run without the

@@ -30,6 +30,17 @@ namespace mpir_hip {
 Entry g_table[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+
+// Strided rows of at least this many bytes take the wide form (one row's tiles
+// per G workgroups), shorter ones the narrow form (rows flattened into units):
+// MPIR_CVAR_REDUCE_LOCAL_STRIDED_WIDE_KB, default 16, one tile (DESIGN.md §Strided
+// reductions has the sweep behind it); MPIR_Hip_set_strided_wide_bytes() at run
+// time.  At most 1 GiB, so that a narrow row's units fit 32 bits.
+constexpr uint64_t kStridedWideMax = (uint64_t)1 << 30;
+std::atomic<uint64_t> g_strided_wide{(uint64_t)cvar_long("MPIR_CVAR_REDUCE_LOCAL_STRIDED_WIDE_KB", 0, 1L << 20, 16) << 10};
+// MPIR_Hip_strided_test_max_groups: the calling thread's per-launch workgroup cap (0: kBatchMaxGroups)
+thread_local uint64_t t_strided_cap = 0;
 
 // Results of at most this many bytes are stored sc1 (into the Infinity Cache)
 // rather than nt: MPIR_CVAR_REDUCE_LOCAL_KEEP_MB (0 = every store nt), default
@@ -542,6 +553,86 @@ bool batch_args_ok(const MPIR_Hip_seg *segs, int nsegs, int op, int elem) {
     return g_batch[op][elem].launch && g_batch[op][elem].groups;
 }
 
+// The plan of a strided call (MPIR_Hip_reduce_strided launches it,
+// MPIR_Hip_strided_plan_info reports it): the form, what a workgroup covers and
+// how many rows a launch takes, all O(1) in the number of rows.
+struct StridedPlan {
+    int form;                   // MPIR_HIP_STRIDED_*
+    uint64_t threshold;         // the wide / narrow threshold in force
+    uint64_t row_bytes;
+    uint64_t per;               // WIDE: G, workgroups per row; NARROW: units per workgroup
+    uint64_t upr;               // NARROW: units per row
+    uint64_t rows_per_launch;
+    uint64_t launches, groups;  // over the whole call
+};
+
+// workgroups of one launch of n rows
+uint64_t strided_launch_groups(const StridedPlan &p, uint64_t n) {
+    return p.form == MPIR_HIP_STRIDED_WIDE ? n * p.per : (n * p.upr + p.per - 1) / p.per;
+}
+
+// the argument checks MPIR_Hip_reduce_strided makes before it looks at a
+// pointer; MPIR_HIP_OK with *form EMPTY or SINGLE where that settles the call
+int strided_args(uint64_t in_stride, uint64_t io_stride, uint64_t nblocks, uint64_t blocklen, int op, int elem,
+                 int *form) {
+    if (!pair_in_range(op, elem) || !g_strided[op][elem].launch || !g_batch[op][elem].groups) return MPIR_HIP_ENOKERNEL;
+    *form = MPIR_HIP_STRIDED_EMPTY;
+    if (!nblocks || !blocklen) return MPIR_HIP_OK;
+    const uint64_t esz = g_elem_size[elem];
+    if (blocklen > (~(uint64_t)0 >> 1) / esz) return MPIR_HIP_EARG;
+    const uint64_t row_bytes = blocklen * esz, top = ~(uint64_t)0 - row_bytes;
+    if (nblocks > 1) {
+        if (io_stride < row_bytes) return MPIR_HIP_EARG;                    // output rows would overlap
+        if (io_stride > top / (nblocks - 1) || (in_stride && in_stride > top / (nblocks - 1))) return MPIR_HIP_EARG;
+    }
+    *form = nblocks == 1 || (in_stride == row_bytes && io_stride == row_bytes) ? MPIR_HIP_STRIDED_SINGLE
+                                                                              : MPIR_HIP_STRIDED_WIDE;
+    return MPIR_HIP_OK;
+}
+
+// (for a call strided_args left as WIDE: more than one row, not contiguous)
+void strided_plan(const void *in, uint64_t in_stride, const void *io, uint64_t io_stride, uint64_t nblocks,
+                  uint64_t blocklen, int elem, StridedPlan &p) {
+    const uint64_t esz = g_elem_size[elem];
+    const uint64_t cap = t_strided_cap && t_strided_cap < kBatchMaxGroups ? t_strided_cap : kBatchMaxGroups;
+    p.row_bytes = blocklen * esz;
+    p.threshold = g_strided_wide.load(std::memory_order_relaxed);
+    if (p.row_bytes >= p.threshold) {
+        p.form = MPIR_HIP_STRIDED_WIDE;
+        p.per = strided_row_groups_max(p.row_bytes, esz, io, io_stride);
+        p.upr = 0;
+        p.rows_per_launch = cap / p.per;                // a row is never split between launches
+    } else {
+        const uint64_t all = p.row_bytes | in_stride | io_stride | reinterpret_cast<uintptr_t>(in) |
+                             reinterpret_cast<uintptr_t>(io);
+        const bool vec = esz <= 16 && (all & 15) == 0;
+        const uint64_t unit = vec ? 16 : esz;
+        p.form = vec ? MPIR_HIP_STRIDED_NARROW_VEC : MPIR_HIP_STRIDED_NARROW_ELEMS;
+        p.per = kTileBytes / unit;
+        p.upr = p.row_bytes / unit;
+        // the kernel's per-lane division is 32-bit: a launch's rows stay below 2^32
+        p.rows_per_launch = std::min<uint64_t>(cap * p.per / p.upr, 0xFFFFFFFFull);
+    }
+    p.rows_per_launch = std::min(std::max<uint64_t>(p.rows_per_launch, 1), nblocks);
+    const uint64_t full = nblocks / p.rows_per_launch, rest = nblocks % p.rows_per_launch;
+    p.launches = full + (rest != 0);
+    p.groups = full * strided_launch_groups(p, p.rows_per_launch) + (rest ? strided_launch_groups(p, rest) : 0);
+}
+
+// The launches of a plan: later row ranges with the base pointers advanced.
+// emit(args, groups) per launch, until it returns false.
+template <class F>
+void strided_launches(const StridedPlan &p, const void *in, uint64_t in_stride, void *io, uint64_t io_stride,
+                      uint64_t nblocks, uint64_t blocklen, F emit) {
+    for (uint64_t row0 = 0; row0 < nblocks; row0 += p.rows_per_launch) {
+        const uint64_t n = std::min(p.rows_per_launch, nblocks - row0);
+        const StridedArgs a{static_cast<const char *>(in) + row0 * in_stride, static_cast<char *>(io) + row0 * io_stride,
+                            in_stride, io_stride, blocklen, (uint32_t)n, (uint32_t)p.form,
+                            (uint32_t)(p.form == MPIR_HIP_STRIDED_WIDE ? p.per : p.upr), 0};
+        if (!emit(a, strided_launch_groups(p, n))) return;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -866,6 +957,107 @@ int MPIR_Hip_reduce_batch(const MPIR_Hip_seg *segs, int nsegs, int op, int elem,
         // (launches made before one that failed are still queued on the library stream)
         if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
         if (e != hipSuccess) rc = set_err(e, "batch launch");
+        else if (sync) rc = wait_stream(dev, s);
+    }
+    return rc;
+}
+
+uint64_t MPIR_Hip_set_strided_wide_bytes(uint64_t bytes) {
+    return mpir_hip::g_strided_wide.exchange(std::min(bytes, mpir_hip::kStridedWideMax));
+}
+
+uint64_t MPIR_Hip_strided_test_max_groups(uint64_t groups) {
+    const uint64_t prev = mpir_hip::t_strided_cap;
+    mpir_hip::t_strided_cap = groups;
+    return prev;
+}
+
+int MPIR_Hip_strided_plan_info(const void *inbuf, uint64_t in_stride, const void *inoutbuf, uint64_t io_stride,
+                               uint64_t nblocks, uint64_t blocklen, int op, int elem, uint64_t out[8]) {
+    int form = 0;
+    const int rc = strided_args(in_stride, io_stride, nblocks, blocklen, op, elem, &form);
+    if (rc != MPIR_HIP_OK) return rc;
+    for (int k = 0; k < 8; ++k) out[k] = 0;
+    out[0] = (uint64_t)form;
+    out[6] = mpir_hip::g_strided_wide.load(std::memory_order_relaxed);
+    if (form == MPIR_HIP_STRIDED_EMPTY) return MPIR_HIP_OK;
+    if (form == MPIR_HIP_STRIDED_SINGLE) {
+        // the single call's own plan (MPIR_Hip_plan_info)
+        const plan_fn fn = g_table[op][elem].plan ? g_table[op][elem].plan : g_table[op][elem].wide;
+        if (!fn) return MPIR_HIP_ENOKERNEL;
+        ReducePlan p;
+        fn(inbuf, const_cast<void *>(inoutbuf), nblocks * blocklen, &p);
+        out[1] = 1;
+        out[2] = p.groups;
+        out[7] = nblocks;
+        return MPIR_HIP_OK;
+    }
+    StridedPlan p;
+    strided_plan(inbuf, in_stride, inoutbuf, io_stride, nblocks, blocklen, elem, p);
+    out[0] = (uint64_t)p.form;
+    out[1] = p.launches;
+    out[2] = p.groups;
+    out[3] = p.per;
+    out[7] = p.rows_per_launch;
+    if (p.form == MPIR_HIP_STRIDED_WIDE) {
+        // every row's path, from the function the batch's planner asks (a loop
+        // over rows: this is the test tool, the launch makes none)
+        const char *in = static_cast<const char *>(inbuf), *io = static_cast<const char *>(inoutbuf);
+        for (uint64_t r = 0; r < nblocks; ++r) {
+            int tile = 0;
+            (void)g_batch[op][elem].groups(in + r * in_stride, io + r * io_stride, blocklen, &tile);
+            ++out[tile ? 4 : 5];
+        }
+    }
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_reduce_strided(const void *inbuf, uint64_t in_stride, void *inoutbuf, uint64_t io_stride,
+                            uint64_t nblocks, uint64_t blocklen, int op, int elem, void *hip_stream, int sync) {
+    int form = 0;
+    int rc = strided_args(in_stride, io_stride, nblocks, blocklen, op, elem, &form);
+    if (rc != MPIR_HIP_OK || form == MPIR_HIP_STRIDED_EMPTY) return rc;
+    ctx().err[0] = 0;
+    // the first and the last byte of each operand's span, before anything is
+    // launched: a call that fails has written nothing
+    const uint64_t row_bytes = blocklen * g_elem_size[elem];
+    const char *in = static_cast<const char *>(inbuf);
+    char *io = static_cast<char *>(inoutbuf);
+    const void *ends[4] = {in, in + (nblocks - 1) * in_stride + row_bytes - 1, io,
+                           io + (nblocks - 1) * io_stride + row_bytes - 1};
+    int dev = -1;
+    DeviceSpan span_in, span_io;
+    for (int k = 0; k < 4; ++k) {
+        int d = -1;
+        if (classify_in_span(ends[k], &d, k < 2 ? span_in : span_io) != LOC_DEVICE || (k && d != dev))
+            return MPIR_HIP_EBUFFER;
+        dev = d;
+    }
+    // one row, or contiguous rows: the single call -- the direct AQL dispatch
+    // when synchronous, every existing plan
+    if (form == MPIR_HIP_STRIDED_SINGLE)
+        return MPIR_Hip_reduce(inbuf, inoutbuf, nblocks * blocklen, op, elem, hip_stream, sync);
+    StridedPlan p;
+    strided_plan(inbuf, in_stride, inoutbuf, io_stride, nblocks, blocklen, elem, p);
+    if (p.form == MPIR_HIP_STRIDED_WIDE && p.per > kBatchMaxGroups) {
+        snprintf(ctx().err, sizeof(ctx().err), "a strided row needs more workgroups than one launch holds");
+        return MPIR_HIP_ERUNTIME;
+    }
+    DeviceScope on(dev);
+    if (!on.ok()) return on.err();
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!s) rc = get_stream(dev, S_MAIN, &s);
+    if (rc == MPIR_HIP_OK) {
+        hipError_t e = hipSuccess;
+        const strided_fn launch = g_strided[op][elem].launch;
+        strided_launches(p, inbuf, in_stride, inoutbuf, io_stride, nblocks, blocklen,
+                         [&](const StridedArgs &a, uint64_t groups) {
+                             e = launch(&a, groups, s);
+                             return e == hipSuccess;
+                         });
+        // (launches made before one that failed are still queued on the library stream)
+        if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
+        if (e != hipSuccess) rc = set_err(e, "strided launch");
         else if (sync) rc = wait_stream(dev, s);
     }
     return rc;

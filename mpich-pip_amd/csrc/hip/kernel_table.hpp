@@ -33,6 +33,7 @@ typedef void (*plan_fn)(const void *, void *, uint64_t, ReducePlan *);
 typedef void (*split_fn)(const void *const *, int, const void *, uint64_t, CombineSplit *);
 typedef hipError_t (*batch_fn)(const BatchArgs *, uint64_t, hipStream_t);
 typedef uint64_t (*bgroups_fn)(const void *, const void *, uint64_t, int *);
+typedef hipError_t (*strided_fn)(const StridedArgs *, uint64_t, hipStream_t);
 
 // plan: plan_reduce<T> (reduce_kernels.hpp) for the classes whose launcher is
 // launch_reduce -- the kernel, grid and argument bytes the direct AQL dispatch
@@ -48,6 +49,11 @@ struct Entry { launch_fn fn; any_fn any; host_fn host; plan_fn plan; plan_fn wid
 // groups = batch_groups_any<T>, a segment's path and workgroup count for the
 // batch's planner.
 struct BatchEntry { batch_fn launch; bgroups_fn groups; };
+// g_strided[op][elem], likewise a table of its own: launch_strided<Op, T>, one
+// launch of k_reduce_strided over a range of rows (MPIR_Hip_reduce_strided), for
+// the pairs g_batch holds (reg_strided<>, from the reg_strided_*.hip units); a
+// row's path and workgroups are g_batch's `groups`.
+struct StridedEntry { strided_fn launch; };
 
 // float / double SUM and PROD on the host: the SSE instruction itself.  The
 // reference's loop `a[i] = a[i] + b[i]` (opsum.c:21-76, gcc -O2) is an
@@ -116,6 +122,7 @@ void host_loop(const void *in, void *io, uint64_t n) {
 }
 extern Entry g_table[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 constexpr int kMultiMaxP = 8;
 extern multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 
@@ -136,6 +143,14 @@ void reg_wide(int op, int elem) {
     g_table[op][elem].host = &host_loop<Op, T>;
     g_table[op][elem].any = &launch_combine_any<Op, T>;
     g_batch[op][elem] = BatchEntry{&launch_batch<Op, T>, &batch_groups_any<T>};
+}
+// the strided kernel of a pair reg<> / reg_wide<> registers (REPLACE has none).
+// Called from units of their own, reg_strided_*.hip, one beside each reg_*.hip
+// with that unit's list of pairs: the code objects of the single call's, the
+// batch's and the folds' kernels stay what they were without this entry point.
+template <class Op, class T>
+void reg_strided(int op, int elem) {
+    g_strided[op][elem] = StridedEntry{&launch_strided<Op, T>};
 }
 template <class Op, class T>
 void reg_multi(int op, int elem) {

@@ -763,6 +763,165 @@ hipError_t launch_batch(const BatchArgs *a, uint64_t groups, hipStream_t s) {
 }
 
 // ============================================================================
+// Strided reductions (MPIR_Hip_reduce_strided): nrows equal rows of blocklen
+// elements, row r at in + r * in_stride and io + r * io_stride (bytes), each
+// row's result what the single call gives on it.  An MPI_Type_vector operand
+// -- a sub-matrix, a halo face, a column -- needs no segment table: five numbers
+// describe it and the workgroup-to-row mapping is arithmetic, so any number of
+// rows is one launch (up to kBatchMaxGroups workgroups), with 56 bytes of kernel
+// arguments.  Two forms, chosen on the host by the row's bytes:
+//
+//   * WIDE (row bytes >= the threshold): the grid is nrows x G, G = the most
+//     workgroups any row can need (strided_row_groups_max).  Workgroup wg takes
+//     row wg / G, tile wg % G, computes that row's pointers and runs the batch's
+//     segment code on them (reduce_seg: seg_split on the device, the 16 KiB tile
+//     grid of the row's own inoutbuf address or the element form).  Rows may
+//     differ in path when the strides differ mod 16; a row that needs fewer than
+//     G workgroups leaves the rest idle, at most one, and none when inoutbuf's
+//     base and stride are multiples of 16 KiB.  The row's pointers come from
+//     blockIdx and the kernel arguments alone, so the tile's buffer descriptors
+//     stay in scalar registers.
+//   * NARROW: the rows flattened into units, workgroup g owning units
+//     [g, g + 1) x 16 KiB / unit bytes wherever they fall -- its span may begin
+//     and end in the middle of a row.  A unit is one 16-byte vector (nt loads
+//     and store, combine16) when the row bytes, both strides and both bases are
+//     multiples of 16 and the element is at most 16 bytes, else one element in
+//     batch_elem_at's form (any alignment).  The workgroup divides its first
+//     unit by the units per row once, in 64 bits; a lane's unit is at most
+//     16383 further on, so its row and column are one 32-bit division.  (Each
+//     lane addresses another row: per-lane global addresses, no descriptor.)
+//
+// No LDS, no scratch, no gridDim: everything comes from the arguments.
+// ============================================================================
+struct StridedArgs {
+    const char *in;         // row 0 of this launch
+    char *io;
+    uint64_t in_stride;     // bytes between rows (0: one input row for every output row)
+    uint64_t io_stride;     // bytes, >= the row's bytes
+    uint64_t blocklen;      // elements per row, > 0
+    uint32_t nrows;         // rows of this launch, > 0
+    uint32_t form;          // MPIR_HIP_STRIDED_WIDE / _NARROW_VEC / _NARROW_ELEMS
+    uint32_t per;           // WIDE: G, workgroups per row; NARROW: units per row
+    uint32_t pad_;
+};
+
+// G of the wide form: the most workgroups batch_seg_groups can give a row of
+// row_bytes, whatever its pointers.  The tile path's count is largest with no
+// head (vbytes = row_bytes rounded down to 16) and the vector region 16 B short
+// of a grid boundary; the element path's is row_bytes / 16 KiB rounded up, never
+// more.  With inoutbuf's base and stride both on the 16 KiB grid every row starts
+// a tile, and the element path's count bounds both.
+inline uint64_t strided_row_groups_max(uint64_t row_bytes, size_t esz, const void *io, uint64_t io_stride) {
+    const uint64_t elems = (row_bytes + kTileBytes - 1) / kTileBytes;
+    const bool on_grid = ((reinterpret_cast<uintptr_t>(io) | io_stride) & (kTileBytes - 1)) == 0;
+    if (esz > 16 || on_grid) return elems ? elems : 1;
+    const uint64_t tiles = ((row_bytes & ~(uint64_t)15) + 2 * (uint64_t)kTileBytes - 17) / kTileBytes;
+    return tiles > elems ? tiles : elems;
+}
+
+// Workgroup `tile` of the segment (in, io, count), all three uniform across the
+// workgroup: its 16 KiB tile of the grid over inoutbuf's address (tile 0 also the
+// head and tail elements), or its run of the element form.  A tile at or past
+// the segment's own workgroup count does nothing.  What k_reduce_batch does for
+// a segment once it has found it, for the strided kernel's wide rows: the split
+// and the workgroup count come from the same seg_split / batch_seg_groups.
+template <class Op, class T>
+__device__ __forceinline__ void reduce_seg(const char *in, char *io, uint64_t count, uint64_t tile) {
+    const SegSplit s = seg_split<T>(in, io, count);
+    if (tile >= batch_seg_groups<T>(s, io, count)) return;
+    if constexpr (sizeof(T) <= 16) {
+        if (s.tile) {
+            reduce_tile<Op, T>(in + s.head_bytes, io + s.head_bytes, tile, s.vbytes, 0);
+            if (tile == 0) {
+                Op op;
+                const unsigned t = threadIdx.x;
+                if (t < s.nhead) {
+                    T *p = reinterpret_cast<T *>(io) + t;
+                    *p = op(*p, reinterpret_cast<const T *>(in)[t]);
+                } else if (t >= 64 && t - 64 < s.ntail) {
+                    T *p = reinterpret_cast<T *>(io + s.head_bytes + s.vbytes) + (t - 64);
+                    *p = op(*p, reinterpret_cast<const T *>(in + s.head_bytes + s.vbytes)[t - 64]);
+                }
+            }
+            return;
+        }
+    }
+    constexpr uint64_t per = kTileBytes / sizeof(T);
+    const uint64_t base = tile * per;
+    const uint64_t end = base + per < count ? base + per : count;
+    for (uint64_t i = base + threadIdx.x; i < end; i += kThreads) batch_elem_at<Op, T>(in, io, i);
+}
+
+// units of the narrow forms: bytes of one, and how many a workgroup owns
+template <class T>
+constexpr uint32_t strided_units_per_group(bool vec) { return kTileBytes / (vec ? 16 : (uint32_t)sizeof(T)); }
+
+template <class Op, class T>
+__device__ __forceinline__ void reduce_strided_narrow(const StridedArgs &a) {
+    const uint32_t upr = a.per;                             // units per row
+    const unsigned t = threadIdx.x;
+    if constexpr (sizeof(T) <= 16) {
+        if (a.form == MPIR_HIP_STRIDED_NARROW_VEC) {
+            constexpr uint32_t upw = strided_units_per_group<T>(true);
+            constexpr int per_lane = (int)(upw / kThreads);
+            const uint64_t u0 = (uint64_t)blockIdx.x * upw;
+            const uint64_t row0 = u0 / upr;
+            const uint32_t col0 = (uint32_t)(u0 - row0 * upr);
+            u32x4 x[per_lane], y[per_lane];
+            u32x4 *po[per_lane];
+            bool ok[per_lane];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                const uint32_t c = col0 + t + (uint32_t)j * kThreads;
+                const uint32_t q = c / upr;
+                const uint64_t row = row0 + q, off = (uint64_t)(c - q * upr) * 16;
+                ok[j] = row < a.nrows;
+                po[j] = reinterpret_cast<u32x4 *>(a.io + row * a.io_stride + off);
+                if (ok[j]) {
+                    x[j] = __builtin_nontemporal_load(po[j]);
+                    y[j] = __builtin_nontemporal_load(reinterpret_cast<const u32x4 *>(a.in + row * a.in_stride + off));
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j)
+                if (ok[j]) __builtin_nontemporal_store(combine16<Op, T>(x[j], y[j]), po[j]);
+            return;
+        }
+    }
+    constexpr uint32_t upw = strided_units_per_group<T>(false);
+    const uint64_t u0 = (uint64_t)blockIdx.x * upw;
+    const uint64_t row0 = u0 / upr;
+    const uint32_t col0 = (uint32_t)(u0 - row0 * upr);
+    for (uint32_t k = t; k < upw; k += kThreads) {
+        const uint32_t c = col0 + k;
+        const uint32_t q = c / upr;
+        const uint64_t row = row0 + q;
+        if (row >= a.nrows) break;                          // rows only grow with k
+        batch_elem_at<Op, T>(a.in + row * a.in_stride, a.io + row * a.io_stride, c - q * upr);
+    }
+}
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_reduce_strided(StridedArgs a) {
+    if (a.form == MPIR_HIP_STRIDED_WIDE) {
+        const uint32_t row = blockIdx.x / a.per;
+        if (row >= a.nrows) return;
+        reduce_seg<Op, T>(a.in + row * a.in_stride, a.io + row * a.io_stride, a.blocklen, blockIdx.x - row * a.per);
+        return;
+    }
+    reduce_strided_narrow<Op, T>(a);
+}
+
+// one launch: `groups` workgroups over a.nrows rows (the planner's count:
+// nrows x G, or the rows' units over the units a workgroup owns, rounded up)
+template <class Op, class T>
+hipError_t launch_strided(const StridedArgs *a, uint64_t groups, hipStream_t s) {
+    if (!a->nrows || !a->per || !a->blocklen || groups < 1 || groups > kBatchMaxGroups) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_reduce_strided<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+// ============================================================================
 // Multi-operand combines: the log2(p) / (p-1) MPIR_Reduce_local steps of a
 // reduction schedule fused into ONE pass over HBM, in the schedule's exact
 // association and operand order (so results are bit-identical to running the

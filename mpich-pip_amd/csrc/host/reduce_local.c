@@ -485,6 +485,79 @@ static int reduce_local_batch(const MPIX_Reduce_local_seg * segs, int nsegs, MPI
     return MPI_SUCCESS;
 }
 
+/* ---- MPIX_Reduce_local_strided: equal rows at one stride (see the header) */
+/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
+#pragma weak MPIR_Hip_reduce_strided
+static int reduce_local_strided(const void *inbuf, MPI_Aint in_stride, void *inoutbuf, MPI_Aint inout_stride,
+                                int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream);
+
+int MPIX_Reduce_local_strided(const void *inbuf, MPI_Aint in_stride, void *inoutbuf, MPI_Aint inout_stride,
+                              int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    int rc;
+    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
+    rc = reduce_local_strided(inbuf, in_stride, inoutbuf, inout_stride, nblocks, blocklen, datatype, op, hip_stream);
+    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
+    return rc;
+}
+
+static int reduce_local_strided(const void *inbuf, MPI_Aint in_stride, void *inoutbuf, MPI_Aint inout_stride,
+                                int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    static const char *fc = "MPIX_Reduce_local_strided";
+    int mpi_errno, opidx, elem, rc;
+    const int empty = nblocks == 0 || blocklen == 0;
+    if (nblocks < 0 || blocklen < 0) {
+        MPIR_Err_set_detail("negative %s %d", nblocks < 0 ? "nblocks" : "blocklen", nblocks < 0 ? nblocks : blocklen);
+        return err_return(fc, MPI_ERR_COUNT);
+    }
+    /* as the batch validates a segment: an empty call's pointers are not looked
+     * at (the op still is) */
+    mpi_errno = empty ? validate(NULL, NULL, 0, datatype, op) : validate(inbuf, inoutbuf, blocklen, datatype, op);
+    if (mpi_errno != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
+    if (in_stride < 0 || inout_stride < 0) {
+        MPIR_Err_set_detail("negative %s", in_stride < 0 ? "in_stride" : "inout_stride");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (empty)
+        return MPI_SUCCESS;
+    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
+        MPIR_Err_set_detail("user MPI_Op functions run on the host; use MPI_Reduce_local");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    opidx = op & 0xf;
+    elem = MPIR_Op_resolve_elem(opidx, datatype);
+    if (!elem) {        /* compute switch `default:` (LAND/LOR on floats) */
+        MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    if (nblocks > 1 && (uint64_t) inout_stride < (uint64_t) blocklen * MPIR_Hip_elem_size(elem)) {
+        MPIR_Err_set_detail("inout_stride %ld is below the row's %lu bytes: output rows would overlap",
+                            (long) inout_stride, (unsigned long) blocklen * MPIR_Hip_elem_size(elem));
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (!MPIR_Hip_reduce_strided) {
+        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_strided");
+        return err_return(fc, MPI_ERR_OTHER);
+    }
+    rc = MPIR_Hip_reduce_strided(inbuf, (uint64_t) in_stride, inoutbuf, (uint64_t) inout_stride, (uint64_t) nblocks,
+                                 (uint64_t) blocklen, opidx, elem, hip_stream, hip_stream == NULL);
+    if (rc == MPIR_HIP_EBUFFER) {
+        MPIR_Err_set_detail("%s needs device-resident buffers on one device", fc);
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (rc == MPIR_HIP_EARG) {
+        MPIR_Err_set_detail("%s: the rows' span does not fit the address space", fc);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (rc != MPIR_HIP_OK) {
+        MPIR_Op_report_hip_error(fc, rc);
+        return err_return(fc, *MPIR_Op_errno_ptr());
+    }
+    return MPI_SUCCESS;
+}
+
 /* ---- MPI_Op_create / MPI_Op_free / MPI_Op_commutative ------------------ */
 int PMPI_Op_create(MPI_User_function * user_fn, int commute, MPI_Op * op)
 {

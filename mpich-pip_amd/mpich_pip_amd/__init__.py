@@ -112,6 +112,8 @@ EXPORTED_SYMBOLS = [
     "MPIX_Reduce_local_stream", "MPIX_Reduce_local_set_errhandler", "MPIX_Reduce_local_get_errhandler",
     "MPIX_Reduce_local_multi", "MPIR_Hip_combine",
     "MPIX_Reduce_local_batch", "MPIR_Hip_reduce_batch", "MPIR_Hip_batch_plan_info",
+    "MPIX_Reduce_local_strided", "MPIR_Hip_reduce_strided", "MPIR_Hip_strided_plan_info",
+    "MPIR_Hip_set_strided_wide_bytes", "MPIR_Hip_strided_test_max_groups",
     # device collectives (include/mpix_hip_coll.h)
     "MPIX_Hip_comm_get_unique_id", "MPIX_Hip_comm_create", "MPIX_Hip_comm_create_loopback",
     "MPIX_Hip_comm_free", "MPIX_Hip_comm_rank", "MPIX_Hip_comm_size",
@@ -181,6 +183,16 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.MPIR_Hip_batch_plan_info.argtypes = [ctypes.POINTER(HipSeg), i32, i32, i32, ctypes.POINTER(ctypes.c_uint64),
                                              ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
     lib.MPIR_Hip_batch_plan_info.restype = i32
+    u64 = ctypes.c_uint64
+    lib.MPIX_Reduce_local_strided.argtypes = [vp, ctypes.c_long, vp, ctypes.c_long, i32, i32, i32, i32, vp]
+    lib.MPIX_Reduce_local_strided.restype = i32
+    lib.MPIR_Hip_reduce_strided.argtypes = [vp, u64, vp, u64, u64, u64, i32, i32, vp, i32]
+    lib.MPIR_Hip_reduce_strided.restype = i32
+    lib.MPIR_Hip_strided_plan_info.argtypes = [vp, u64, vp, u64, u64, u64, i32, i32, ctypes.POINTER(u64)]
+    lib.MPIR_Hip_strided_plan_info.restype = i32
+    for name in ("MPIR_Hip_set_strided_wide_bytes", "MPIR_Hip_strided_test_max_groups"):
+        getattr(lib, name).argtypes = [u64]
+        getattr(lib, name).restype = u64
     lib.MPIX_Hip_comm_get_unique_id.argtypes = [vp]
     lib.MPIX_Hip_comm_get_unique_id.restype = i32
     lib.MPIX_Hip_comm_create.argtypes = [vp, i32, i32, ctypes.POINTER(vp)]
@@ -430,6 +442,43 @@ def batch_plan_info(segs, datatype: int, op: int) -> dict:
     d["seg_kind"] = [int(kind[i]) for i in range(n)]
     d["seg_groups"] = [int(groups[i]) for i in range(n)]
     return d
+
+
+# ---- strided reductions (MPIX_Reduce_local_strided)
+STRIDED_EMPTY, STRIDED_SINGLE, STRIDED_WIDE, STRIDED_NARROW_VEC, STRIDED_NARROW_ELEMS = range(5)
+STRIDED_NAMES = ["empty", "single", "wide", "narrow_vec", "narrow_elems"]
+MPIR_HIP_EARG = 5
+
+
+def reduce_local_strided(inbuf: int, in_stride: int, inoutbuf: int, inout_stride: int, nblocks: int, blocklen: int,
+                         datatype: int, op: int, stream: int = 0) -> int:
+    """MPIX_Reduce_local_strided: nblocks rows of blocklen elements, row r at
+    inbuf + r * in_stride and inoutbuf + r * inout_stride (raw device addresses,
+    strides in bytes), in one launch.  stream 0: synchronous on the library
+    stream; otherwise enqueued on that HIP stream, no wait."""
+    return load().MPIX_Reduce_local_strided(ctypes.c_void_p(inbuf or None), in_stride, ctypes.c_void_p(inoutbuf or None),
+                                            inout_stride, nblocks, blocklen, datatype, op,
+                                            ctypes.c_void_p(stream or None))
+
+
+def strided_plan_info(inbuf: int, in_stride: int, inoutbuf: int, inout_stride: int, nblocks: int, blocklen: int,
+                      datatype: int, op: int) -> dict:
+    """MPIR_Hip_strided_plan_info: the launches of a strided reduction of device
+    operands at these addresses (never dereferenced; no GPU needed): form
+    (STRIDED_*), launches, groups (over all launches), per (WIDE: G, workgroups
+    per row; NARROW: units per workgroup), tile_rows / elem_rows (WIDE: rows per
+    path), threshold (bytes from which a row is wide) and rows_per_launch.
+    Raises LookupError where the pair has no kernel, ValueError for strides the
+    call refuses."""
+    out = (ctypes.c_uint64 * 8)()
+    rc = load().MPIR_Hip_strided_plan_info(ctypes.c_void_p(inbuf or None), in_stride, ctypes.c_void_p(inoutbuf or None),
+                                           inout_stride, nblocks, blocklen, op & 0xFF, _ELEM_BY_HANDLE[datatype], out)
+    if rc == MPIR_HIP_EARG:
+        raise ValueError("MPIR_Hip_strided_plan_info: strides refused")
+    if rc:
+        raise LookupError(f"MPIR_Hip_strided_plan_info: {rc}")
+    return dict(zip(("form", "launches", "groups", "per", "tile_rows", "elem_rows", "threshold", "rows_per_launch"),
+                    (int(v) for v in out)))
 
 
 MPIX_HIP_ALG_AUTO = 0
