@@ -304,6 +304,53 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_batch(const MPIX_Reduce_local_seg *segs, 
 MPICH_API_PUBLIC int MPIX_Reduce_local_strided(const void *inbuf, MPI_Aint in_stride,
                               void *inoutbuf, MPI_Aint inout_stride, int nblocks, int blocklen,
                               MPI_Datatype datatype, MPI_Op op, void *hip_stream);
+/* Fetching local reduction: the old value out and the combine in one pass -- the
+ * target side of MPI_Get_accumulate / MPI_Fetch_and_op, which copies the target's
+ * old contents into the response buffer and then combines the origin's data into
+ * the target (src/mpid/ch3/src/ch3u_rma_pkthandler.c:899-917 "NOTE: 'copy data +
+ * ACC' needs to be atomic", :1354; ch3u_handle_recv_req.c:207, 274, 356, 441, 494,
+ * 1350, 1423, 1567), and any schedule step that must keep the previous partial
+ * result while it folds the next operand into it.  For i in [0, count):
+ *   fetchbuf[i] receives the bytes inoutbuf[i] held on entry;
+ *   inoutbuf[i] becomes what MPI_Reduce_local(inbuf, inoutbuf, count, datatype, op)
+ *       would have left there, bit for bit.
+ * One kernel launch and four streams through memory, where a device copy followed
+ * by MPI_Reduce_local is two launches and reads inoutbuf twice.
+ *   The fetched bytes are a byte copy of count x the datatype's size bytes, never
+ *       passed through an arithmetic type: NaN payloads and the six padding bytes
+ *       of each x87 long double slot arrive as they were.
+ *   The value combined and the value fetched come from one and the same read of
+ *       inoutbuf[i]: the reference's atomicity requirement holds by construction.
+ *   Ops: the builtin ops on basic types, validated as MPIR_ERRTEST_OP_GACC
+ *       (src/include/mpir_err.h:528-539) plus MPI_Reduce_local's datatype check.
+ *       MPI_OP_NULL and invalid handles: MPI_ERR_OP; user ops: MPI_ERR_OP (not
+ *       predefined); MPI_LAND / MPI_LOR on floating types: MPI_ERR_OP, as
+ *       everywhere in this library.  MPI_NO_OP and MPI_REPLACE, which every other
+ *       entry point refuses, are accepted on every basic type; on a derived
+ *       handle they are MPI_ERR_TYPE, as MPIR_REPLACE answers.
+ *   MPI_NO_OP (an atomic get) never looks at inbuf, which may be NULL; inoutbuf is
+ *       not written; fetchbuf receives the copy.  MPI_REPLACE (a swap) puts the old
+ *       bytes in fetchbuf and sets inoutbuf = inbuf.  Both are stream-ordered
+ *       device copies, no kernel.
+ *   count < 0 is MPI_ERR_COUNT.  count == 0 succeeds and no pointer is looked at.
+ *   inbuf == inoutbuf: MPI_ERR_BUFFER under MPIR_CVAR_COLL_ALIAS_CHECK.
+ *       MPI_IN_PLACE for any of the three buffers: MPI_ERR_BUFFER.  fetchbuf NULL
+ *       with count > 0: MPI_ERR_BUFFER.  fetchbuf's byte range overlapping
+ *       inoutbuf's, or inbuf's unless the op is MPI_NO_OP: MPI_ERR_BUFFER, checked
+ *       whatever the alias check says, as MPIX_Reduce_local_multi checks its output
+ *       against its operands.  An inbuf range partly overlapping inoutbuf stays
+ *       undefined, as elsewhere.
+ *   All buffers that are looked at must be device-resident on one device (else
+ *       MPI_ERR_BUFFER).  Host operands are not taken, as the batch and the strided
+ *       call refuse them.
+ *   Everything is validated and classified before the first launch: a call that
+ *       returns an error has written nothing.
+ *   hip_stream NULL: synchronous on the calling thread's library stream, both
+ *       results complete on return; otherwise enqueued on that stream without
+ *       waiting.  The call is self-contained in its kernel arguments and can be
+ *       captured into a HIP graph. */
+MPICH_API_PUBLIC int MPIX_Reduce_local_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, int count,
+                            MPI_Datatype datatype, MPI_Op op, void *hip_stream);
 MPICH_API_PUBLIC int MPIX_Reduce_local_set_errhandler(MPI_Errhandler errhandler);
 MPICH_API_PUBLIC int MPIX_Reduce_local_get_errhandler(MPI_Errhandler * errhandler);
 

@@ -192,6 +192,45 @@ uint64_t MPIR_Hip_set_strided_wide_bytes(uint64_t bytes);
  * Returns the previous value. */
 uint64_t MPIR_Hip_strided_test_max_groups(uint64_t groups);
 
+/* Fetching reduction: for i < count, fetchbuf[i] = the bytes inoutbuf[i] held on
+ * entry and inoutbuf[i] = op(inoutbuf[i], inbuf[i]), in one kernel launch that
+ * reads inoutbuf once -- the target side of MPI_Get_accumulate / MPI_Fetch_and_op
+ * (ch3u_rma_pkthandler.c:899-917, :1354; ch3u_handle_recv_req.c:207, 274, 356,
+ * 441, 494, 1350, 1423, 1567), whose "copy data + ACC" the reference requires to
+ * be atomic: the value fetched and the value combined come from the same load.
+ * inoutbuf's result is bit-identical to MPIR_Hip_reduce's; the fetched bytes are
+ * a byte copy of count * MPIR_Hip_elem_size(elem) bytes.
+ * op: an MPIR_Hip_op with a kernel for elem, or one of the two copy ops, which
+ * need no kernel and take any element class:
+ *   MPIR_HIP_OP_NO_OP    fetchbuf <- inoutbuf: one stream-ordered device copy;
+ *                        inbuf is never looked at (it may be NULL), inoutbuf
+ *                        is not written;
+ *   MPIR_HIP_OP_REPLACE  fetchbuf <- inoutbuf, then inoutbuf <- inbuf: two such
+ *                        copies on the same stream.
+ * count == 0 succeeds with no pointer looked at.  Every buffer that is looked at
+ * must be device-resident, all on one device (else MPIR_HIP_EBUFFER; host
+ * operands are not taken); they are classified before the first launch, so a
+ * call that fails has written nothing.  fetchbuf overlapping either operand is
+ * undefined here (MPIX_Reduce_local_fetch refuses it).  hip_stream / sync as for
+ * MPIR_Hip_reduce; the launch carries everything in its kernel arguments.
+ * MPIR_HIP_ENOKERNEL for pairs with no kernel. */
+#define MPIR_HIP_OP_NO_OP 14   /* MPI_NO_OP's table index; MPIR_Hip_reduce_fetch alone takes it (no kernel table slot) */
+int MPIR_Hip_reduce_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, uint64_t count, int op, int elem,
+                          void *hip_stream, int sync);
+
+/* For tests and tools: the plan MPIR_Hip_reduce_fetch would take for device
+ * operands at these addresses, from the planner the launch runs (host
+ * arithmetic on the pointer values only).  out = {path, workgroups, nhead,
+ * ntail}: the path below, the grid of the one launch (0 for EMPTY and COPY), and
+ * the elements workgroup 0 takes before / after the 16-byte vector region on the
+ * tile path (0 on the others). */
+#define MPIR_HIP_FETCH_EMPTY 0   /* count == 0: nothing to do */
+#define MPIR_HIP_FETCH_COPY  1   /* MPI_NO_OP / MPI_REPLACE: device copies, no kernel */
+#define MPIR_HIP_FETCH_TILE  2   /* all three pointers naturally aligned, one offset mod 16: the 16 KiB tile grid */
+#define MPIR_HIP_FETCH_ELEMS 3   /* any other alignment, and the 32-byte classes: element runs */
+int MPIR_Hip_fetch_plan_info(const void *inbuf, const void *inoutbuf, const void *fetchbuf, uint64_t count, int op,
+                             int elem, uint64_t out[4]);
+
 /* Flags for the calling thread's later MPIR_Hip_combine calls; returns the
  * previous flags.  MPIR_HIP_COMBINE_UNCAPPED: the fused folds run without the
  * LDS reservation that caps a CU at one (P >= 5) or three (P = 3, 4) of their

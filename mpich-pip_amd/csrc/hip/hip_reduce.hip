@@ -31,6 +31,7 @@ Entry g_table[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 
 // Strided rows of at least this many bytes take the wide form (one row's tiles
 // per G workgroups), shorter ones the narrow form (rows flattened into units):
@@ -633,6 +634,19 @@ void strided_launches(const StridedPlan &p, const void *in, uint64_t in_stride, 
     }
 }
 
+// the argument checks MPIR_Hip_reduce_fetch makes before it looks at a pointer;
+// MPIR_HIP_OK with *path EMPTY or COPY where that settles the call, else TILE
+// (the plan then says which of the kernel's two paths)
+int fetch_args(uint64_t count, int op, int elem, int *path) {
+    const bool copy = op == MPIR_HIP_OP_NO_OP || op == MPIR_HIP_OP_REPLACE;
+    if (elem <= 0 || elem >= MPIR_HIP_NELEMS) return MPIR_HIP_ENOKERNEL;
+    if (!copy && (!pair_in_range(op, elem) || !g_fetch[op][elem].launch || !g_fetch[op][elem].plan))
+        return MPIR_HIP_ENOKERNEL;
+    if (count > (~(uint64_t)0 >> 1) / g_elem_size[elem]) return MPIR_HIP_EARG;
+    *path = !count ? MPIR_HIP_FETCH_EMPTY : copy ? MPIR_HIP_FETCH_COPY : MPIR_HIP_FETCH_TILE;
+    return MPIR_HIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1058,6 +1072,76 @@ int MPIR_Hip_reduce_strided(const void *inbuf, uint64_t in_stride, void *inoutbu
         // (launches made before one that failed are still queued on the library stream)
         if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
         if (e != hipSuccess) rc = set_err(e, "strided launch");
+        else if (sync) rc = wait_stream(dev, s);
+    }
+    return rc;
+}
+
+int MPIR_Hip_fetch_plan_info(const void *inbuf, const void *inoutbuf, const void *fetchbuf, uint64_t count, int op,
+                             int elem, uint64_t out[4]) {
+    int path = 0;
+    const int rc = fetch_args(count, op, elem, &path);
+    if (rc != MPIR_HIP_OK) return rc;
+    out[0] = (uint64_t)path;
+    out[1] = out[2] = out[3] = 0;
+    if (path != MPIR_HIP_FETCH_TILE) return MPIR_HIP_OK;
+    const FetchArgs a{static_cast<const char *>(inbuf), static_cast<char *>(const_cast<void *>(inoutbuf)),
+                      static_cast<char *>(const_cast<void *>(fetchbuf)), count};
+    FetchPlan p;
+    g_fetch[op][elem].plan(&a, &p);
+    out[0] = p.tile ? MPIR_HIP_FETCH_TILE : MPIR_HIP_FETCH_ELEMS;
+    out[1] = p.groups;
+    out[2] = p.nhead;
+    out[3] = p.ntail;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_reduce_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, uint64_t count, int op, int elem,
+                          void *hip_stream, int sync) {
+    int path = 0;
+    int rc = fetch_args(count, op, elem, &path);
+    if (rc != MPIR_HIP_OK || path == MPIR_HIP_FETCH_EMPTY) return rc;
+    ctx().err[0] = 0;
+    // the first and the last byte of every buffer the call looks at (NO_OP never
+    // looks at inbuf), and the kernel's plan, before anything is enqueued: a call
+    // that fails has written nothing
+    const uint64_t bytes = count * g_elem_size[elem];
+    const char *in = static_cast<const char *>(inbuf);
+    char *io = static_cast<char *>(inoutbuf), *fe = static_cast<char *>(fetchbuf);
+    const void *ends[6] = {io, io + bytes - 1, fe, fe + bytes - 1, in, in ? in + bytes - 1 : in};
+    DeviceSpan span[3];
+    int dev = -1;
+    for (int k = 0; k < (op == MPIR_HIP_OP_NO_OP ? 4 : 6); ++k) {
+        int d = -1;
+        if (classify_in_span(ends[k], &d, span[k / 2]) != LOC_DEVICE || (k && d != dev)) return MPIR_HIP_EBUFFER;
+        dev = d;
+    }
+    const FetchArgs a{in, io, fe, count};
+    if (path == MPIR_HIP_FETCH_TILE) {
+        FetchPlan p;
+        g_fetch[op][elem].plan(&a, &p);
+        if (p.groups > kBatchMaxGroups) {
+            snprintf(ctx().err, sizeof(ctx().err), "a fetching reduction of this size needs more workgroups than one launch holds");
+            return MPIR_HIP_ERUNTIME;
+        }
+    }
+    DeviceScope on(dev);
+    if (!on.ok()) return on.err();
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!s) rc = get_stream(dev, S_MAIN, &s);
+    if (rc == MPIR_HIP_OK) {
+        hipError_t e;
+        if (path == MPIR_HIP_FETCH_COPY) {
+            // stream-ordered device copies: the old bytes out, then (REPLACE) the new ones in
+            e = hipMemcpyAsync(fe, io, bytes, hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess && op == MPIR_HIP_OP_REPLACE && in != io)
+                e = hipMemcpyAsync(io, in, bytes, hipMemcpyDeviceToDevice, s);
+        } else {
+            e = g_fetch[op][elem].launch(&a, s);
+        }
+        // (a copy enqueued before one that failed is still queued on the library stream)
+        if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
+        if (e != hipSuccess) rc = set_err(e, "fetch launch");
         else if (sync) rc = wait_stream(dev, s);
     }
     return rc;

@@ -34,6 +34,8 @@ typedef void (*split_fn)(const void *const *, int, const void *, uint64_t, Combi
 typedef hipError_t (*batch_fn)(const BatchArgs *, uint64_t, hipStream_t);
 typedef uint64_t (*bgroups_fn)(const void *, const void *, uint64_t, int *);
 typedef hipError_t (*strided_fn)(const StridedArgs *, uint64_t, hipStream_t);
+typedef hipError_t (*fetch_fn)(const FetchArgs *, hipStream_t);
+typedef void (*fplan_fn)(const FetchArgs *, FetchPlan *);
 
 // plan: plan_reduce<T> (reduce_kernels.hpp) for the classes whose launcher is
 // launch_reduce -- the kernel, grid and argument bytes the direct AQL dispatch
@@ -54,6 +56,12 @@ struct BatchEntry { batch_fn launch; bgroups_fn groups; };
 // the pairs g_batch holds (reg_strided<>, from the reg_strided_*.hip units); a
 // row's path and workgroups are g_batch's `groups`.
 struct StridedEntry { strided_fn launch; };
+// g_fetch[op][elem], likewise: launch_fetch<Op, T>, the one launch of
+// k_reduce_fetch (MPIR_Hip_reduce_fetch), for the pairs g_batch holds
+// (reg_fetch<>, from the reg_fetch_*.hip units); plan = fetch_plan<T>, the plan
+// that launch makes, for MPIR_Hip_fetch_plan_info.  MPI_NO_OP and MPI_REPLACE
+// are device copies and have no entry.
+struct FetchEntry { fetch_fn launch; fplan_fn plan; };
 
 // float / double SUM and PROD on the host: the SSE instruction itself.  The
 // reference's loop `a[i] = a[i] + b[i]` (opsum.c:21-76, gcc -O2) is an
@@ -123,6 +131,7 @@ void host_loop(const void *in, void *io, uint64_t n) {
 extern Entry g_table[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 constexpr int kMultiMaxP = 8;
 extern multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 
@@ -151,6 +160,11 @@ void reg_wide(int op, int elem) {
 template <class Op, class T>
 void reg_strided(int op, int elem) {
     g_strided[op][elem] = StridedEntry{&launch_strided<Op, T>};
+}
+// the fetching kernel of the same pairs, from the reg_fetch_*.hip units
+template <class Op, class T>
+void reg_fetch(int op, int elem) {
+    g_fetch[op][elem] = FetchEntry{&launch_fetch<Op, T>, &fetch_plan<T>};
 }
 template <class Op, class T>
 void reg_multi(int op, int elem) {

@@ -922,6 +922,150 @@ hipError_t launch_strided(const StridedArgs *a, uint64_t groups, hipStream_t s) 
 }
 
 // ============================================================================
+// Fetching reductions (MPIR_Hip_reduce_fetch): fetch[i] = the bytes io[i] held,
+// io[i] = op(io[i], in[i]), in ONE pass -- the target side of MPI_Get_accumulate
+// and MPI_Fetch_and_op, which copies the target's old contents into the response
+// buffer and then combines the origin's data into the target
+// (ch3u_rma_pkthandler.c:899-917: "NOTE: 'copy data + ACC' needs to be atomic").
+// A device copy followed by the single call reads inoutbuf twice, five streams
+// through HBM; here the tile already holds each 16-byte vector of inoutbuf in
+// registers before it combines, and storing that vector to a third buffer first
+// adds no load and no arithmetic: four streams, one launch.
+//
+//   * One read of inoutbuf: the value stored to fetchbuf and the value combined
+//     are the SAME registers, filled by one load of io[i] -- on the tile path
+//     the vector a[u], on the element path the bytes `old`.  No second read of
+//     inoutbuf exists in the kernel, so the reference's "copy + ACC is atomic"
+//     holds by construction (nothing can come between a copy and a combine that
+//     are one load).
+//   * The fetched bytes are a byte copy: whole 16-byte vectors on the tile path,
+//     an element's raw bytes on the element path (never a value of type T: NaN
+//     payloads and the padding of the x87 slots and of the pair types arrive as
+//     they were).
+//   * Tile path: all three pointers naturally aligned and at one offset mod 16
+//     (fetch_split: seg_split's condition and arithmetic, extended to the third
+//     pointer).  reduce_fetch_tile is reduce_tile with a third buffer descriptor
+//     at the same lo / nrec: the 16 KiB grid is inoutbuf's address grid, and
+//     fetchbuf shares inoutbuf's offset mod 16, not necessarily mod 16 KiB, as
+//     inbuf does.  Both stores are nt (keep = 0, as the batch and the strided
+//     call store).  Tile 0 also takes the head and tail elements.
+//   * Every other alignment, and the 32-byte classes: the element form,
+//     workgroup g owning elements [g, g + 1) x kTileBytes / sizeof(T).
+//   * fetch_split / batch_seg_groups are the one source of the split and the
+//     workgroup count, on the host (fetch_plan) and on the device.
+// 256 threads, 32 bytes of kernel arguments, no LDS, no scratch, no gridDim.
+// ============================================================================
+struct FetchArgs {
+    const char *in;
+    char *io;
+    char *fetch;
+    uint64_t count;     // elements, > 0
+};
+
+// count is an int at the public entry point: at most (2^31 - 1) elements of at
+// most 32 bytes is below 2^36 bytes, so 2^22 tiles of 16 KiB plus the one a
+// start off the grid adds -- one launch always stays below kBatchMaxGroups.
+static_assert(((uint64_t)INT32_MAX * 32 + 2 * (uint64_t)kTileBytes) / kTileBytes < kBatchMaxGroups,
+              "a fetching reduction of INT_MAX elements must fit one launch");
+
+// seg_split of (in, io, count), and the tile path only if fetch sits at io's
+// offset mod 16 as well (it is then naturally aligned where io is)
+template <class T>
+__host__ __device__ inline SegSplit fetch_split(const void *in, const void *io, const void *fetch, uint64_t count) {
+    SegSplit s = seg_split<T>(in, io, count);
+    if (s.tile && ((reinterpret_cast<uintptr_t>(fetch) ^ reinterpret_cast<uintptr_t>(io)) & 15) != 0)
+        s = SegSplit{false, 0, 0, 0, 0};
+    return s;
+}
+
+// element i: its bytes read once, stored to fetch as they are, then combined
+template <class Op, class T>
+__device__ __forceinline__ void fetch_elem_at(const char *in, char *io, char *fetch, uint64_t i) {
+    struct Raw { unsigned char b[sizeof(T)]; };
+    Op op;
+    Raw old;
+    T y;
+    __builtin_memcpy(&old, io + i * sizeof(T), sizeof(T));
+    __builtin_memcpy(&y, in + i * sizeof(T), sizeof(T));
+    __builtin_memcpy(fetch + i * sizeof(T), &old, sizeof(T));
+    const T x = op(__builtin_bit_cast(T, old), y);
+    __builtin_memcpy(io + i * sizeof(T), &x, sizeof(T));
+}
+
+// reduce_tile with the loaded inoutbuf vectors also stored to fetch, through a
+// descriptor of its own clipped where the other two are
+template <class Op, class T>
+__device__ __forceinline__ void reduce_fetch_tile(const char *in, char *io, char *fetch, uint64_t tile, uint64_t vbytes) {
+    const int64_t start = (int64_t)(tile * kTileBytes) - (int64_t)tile_shift(io);
+    const uint64_t lo = start > 0 ? (uint64_t)start : 0;
+    if (lo >= vbytes) return;
+    const uint64_t end = (uint64_t)(start + kTileBytes);
+    const int nrec = (int)((end < vbytes ? end : vbytes) - lo);
+    const int cut = (int)(lo - start);       // 0, or s for tile 0: lanes below it wrap out of range
+    __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)(in + lo), 0, nrec, 0x00020000);
+    __amdgpu_buffer_rsrc_t rio = __builtin_amdgcn_make_buffer_rsrc((void *)(io + lo), 0, nrec, 0x00020000);
+    __amdgpu_buffer_rsrc_t rfe = __builtin_amdgcn_make_buffer_rsrc((void *)(fetch + lo), 0, nrec, 0x00020000);
+    const int t = (int)threadIdx.x;
+    const int wb = (t >> 6) * (kVecPerLane * 1024) + (t & 63) * 16 - cut;
+    u32x4 a[kVecPerLane], b[kVecPerLane];
+#pragma unroll
+    for (int u = 0; u < kVecPerLane; ++u) {
+        a[u] = __builtin_amdgcn_raw_buffer_load_b128(rio, wb + u * 1024, 0, kCachePolicyNT);
+        b[u] = __builtin_amdgcn_raw_buffer_load_b128(rin, wb + u * 1024, 0, kCachePolicyNT);
+        if (u + 1 < kVecPerLane) issue_gap();
+    }
+#pragma unroll
+    for (int u = 0; u < kVecPerLane; ++u) store16(a[u], rfe, wb + u * 1024, false);
+#pragma unroll
+    for (int u = 0; u < kVecPerLane; ++u) store16(combine16<Op, T>(a[u], b[u]), rio, wb + u * 1024, false);
+}
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_reduce_fetch(FetchArgs a) {
+    const uint64_t tile = blockIdx.x;
+    const SegSplit s = fetch_split<T>(a.in, a.io, a.fetch, a.count);
+    if (tile >= batch_seg_groups<T>(s, a.io, a.count)) return;
+    if constexpr (sizeof(T) <= 16) {
+        if (s.tile) {
+            reduce_fetch_tile<Op, T>(a.in + s.head_bytes, a.io + s.head_bytes, a.fetch + s.head_bytes, tile, s.vbytes);
+            if (tile == 0) {
+                const unsigned t = threadIdx.x;
+                const uint64_t tail0 = (s.head_bytes + s.vbytes) / sizeof(T);
+                if (t < s.nhead) fetch_elem_at<Op, T>(a.in, a.io, a.fetch, t);
+                else if (t >= 64 && t - 64 < s.ntail) fetch_elem_at<Op, T>(a.in, a.io, a.fetch, tail0 + (t - 64));
+            }
+            return;
+        }
+    }
+    constexpr uint64_t per = kTileBytes / sizeof(T);
+    const uint64_t base = tile * per;
+    const uint64_t end = base + per < a.count ? base + per : a.count;
+    for (uint64_t i = base + threadIdx.x; i < end; i += kThreads) fetch_elem_at<Op, T>(a.in, a.io, a.fetch, i);
+}
+
+// The plan of one fetching reduction: the path, the grid and tile 0's elements
+// (MPIR_Hip_fetch_plan_info reports it, launch_fetch launches it)
+struct FetchPlan {
+    bool tile;
+    uint64_t groups;
+    uint32_t nhead, ntail;
+};
+template <class T>
+void fetch_plan(const FetchArgs *a, FetchPlan *p) {
+    const SegSplit s = fetch_split<T>(a->in, a->io, a->fetch, a->count);
+    *p = FetchPlan{s.tile, batch_seg_groups<T>(s, a->io, a->count), s.nhead, s.ntail};
+}
+
+template <class Op, class T>
+hipError_t launch_fetch(const FetchArgs *a, hipStream_t s) {
+    FetchPlan p;
+    fetch_plan<T>(a, &p);
+    if (!a->count || p.groups < 1 || p.groups > kBatchMaxGroups) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_reduce_fetch<Op, T>), dim3((unsigned)p.groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+// ============================================================================
 // Multi-operand combines: the log2(p) / (p-1) MPIR_Reduce_local steps of a
 // reduction schedule fused into ONE pass over HBM, in the schedule's exact
 // association and operand order (so results are bit-identical to running the

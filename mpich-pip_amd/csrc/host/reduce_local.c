@@ -558,6 +558,122 @@ static int reduce_local_strided(const void *inbuf, MPI_Aint in_stride, void *ino
     return MPI_SUCCESS;
 }
 
+/* ---- MPIX_Reduce_local_fetch: old value out, combine in (see the header) */
+/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
+#pragma weak MPIR_Hip_reduce_fetch
+static int reduce_local_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, int count, MPI_Datatype datatype,
+                              MPI_Op op, void *hip_stream);
+
+int MPIX_Reduce_local_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, int count, MPI_Datatype datatype,
+                            MPI_Op op, void *hip_stream)
+{
+    int rc;
+    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
+    rc = reduce_local_fetch(inbuf, inoutbuf, fetchbuf, count, datatype, op, hip_stream);
+    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
+    return rc;
+}
+
+static int ranges_overlap(const void *a, const void *b, uint64_t bytes)
+{
+    const uintptr_t pa = (uintptr_t) a, pb = (uintptr_t) b;
+    return pa < pb + bytes && pb < pa + bytes;
+}
+
+static int reduce_local_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, int count, MPI_Datatype datatype,
+                              MPI_Op op, void *hip_stream)
+{
+    static const char *fc = "MPIX_Reduce_local_fetch";
+    const int no_op = op == MPI_NO_OP, copy = no_op || op == MPI_REPLACE;
+    int mpi_errno, opidx, elem, rc;
+    uint64_t n = count > 0 ? (uint64_t) count : 0, bytes;
+    if (count < 0) {
+        MPIR_Err_set_detail("negative count %d", count);
+        return err_return(fc, MPI_ERR_COUNT);
+    }
+    /* MPIR_ERRTEST_OP_GACC (mpir_err.h:528-539): MPI_NO_OP and MPI_REPLACE pass,
+     * a user op does not */
+    if (op == MPI_OP_NULL) {
+        MPIR_Err_set_detail("Null MPI_Op");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    if (HANDLE_GET_MPI_KIND(op) != MPIR_OP_OBJ_KIND || HANDLE_GET_KIND(op) == HANDLE_KIND_INVALID ||
+        (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN && !user_op_get(op)) ||
+        (HANDLE_GET_KIND(op) == HANDLE_KIND_BUILTIN &&
+         ((op & 0xf) >= MPIR_OP_N_BUILTIN || !MPIR_OP_HDL_TO_DTYPE_FN(op)))) {
+        MPIR_Err_set_detail("Invalid MPI_Op");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
+        MPIR_Err_set_detail("MPI_Op is not a predefined operation; user MPI_Op functions run on the host");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    opidx = op & 0xf;
+    if (copy) {
+        /* every predefined datatype is count * size contiguous bytes, as for
+         * MPIR_REPLACE (op_kernels.c); a derived one needs MPICH's datatype engine */
+        const MPIR_Type_desc *d = MPIR_Type_lookup(datatype);
+        const unsigned h = (unsigned) datatype;
+        if (d) {
+            elem = d->elem;
+        } else if ((h >> 30) == 1u && ((h >> 26) & 0xfu) == 0x3u) {     /* builtin-kind datatype */
+            elem = MPIR_HIP_U8;
+            n *= (h >> 8) & 0xffu;
+        } else {
+            MPIR_Err_set_detail("%s: derived datatypes are not supported by this library", no_op ? "MPI_NO_OP" : "MPI_REPLACE");
+            return err_return(fc, MPI_ERR_TYPE);
+        }
+    } else {
+        /* MPI_Reduce_local's datatype check (reduce_local.c:179-183), then the
+         * compute switch's `default:` (LAND / LOR on floats) */
+        mpi_errno = MPIR_OP_HDL_TO_DTYPE_FN(op) (datatype);
+        if (mpi_errno != MPI_SUCCESS)
+            return err_return(fc, mpi_errno);
+        elem = MPIR_Op_resolve_elem(opidx, datatype);
+        if (!elem) {
+            MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
+            return err_return(fc, MPI_ERR_OP);
+        }
+    }
+    if (n == 0)         /* no pointer is looked at */
+        return MPI_SUCCESS;
+    bytes = n * MPIR_Hip_elem_size(elem);
+    /* MPI_NO_OP never looks at inbuf */
+    if (!no_op && alias_check_enabled() && inbuf == inoutbuf) {
+        MPIR_Err_set_detail("Buffers must not be aliased");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if ((!no_op && inbuf == MPI_IN_PLACE) || inoutbuf == MPI_IN_PLACE || fetchbuf == MPI_IN_PLACE) {
+        MPIR_Err_set_detail("buffer '%s' cannot be MPI_IN_PLACE",
+                            !no_op && inbuf == MPI_IN_PLACE ? "inbuf" : inoutbuf == MPI_IN_PLACE ? "inoutbuf" : "fetchbuf");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (!fetchbuf) {
+        MPIR_Err_set_detail("Null buffer pointer 'fetchbuf'");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    /* whatever MPIR_CVAR_COLL_ALIAS_CHECK says, as MPIX_Reduce_local_multi checks
+     * its output against its operands: the old bytes must not land on either */
+    if (ranges_overlap(fetchbuf, inoutbuf, bytes) || (!no_op && ranges_overlap(fetchbuf, inbuf, bytes))) {
+        MPIR_Err_set_detail("fetchbuf overlaps %s", ranges_overlap(fetchbuf, inoutbuf, bytes) ? "inoutbuf" : "inbuf");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (!MPIR_Hip_reduce_fetch) {
+        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_fetch");
+        return err_return(fc, MPI_ERR_OTHER);
+    }
+    rc = MPIR_Hip_reduce_fetch(inbuf, inoutbuf, fetchbuf, n, opidx, elem, hip_stream, hip_stream == NULL);
+    if (rc == MPIR_HIP_EBUFFER) {
+        MPIR_Err_set_detail("%s needs device-resident buffers on one device", fc);
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (rc != MPIR_HIP_OK) {
+        MPIR_Op_report_hip_error(fc, rc);
+        return err_return(fc, *MPIR_Op_errno_ptr());
+    }
+    return MPI_SUCCESS;
+}
+
 /* ---- MPI_Op_create / MPI_Op_free / MPI_Op_commutative ------------------ */
 int PMPI_Op_create(MPI_User_function * user_fn, int commute, MPI_Op * op)
 {

@@ -114,6 +114,7 @@ EXPORTED_SYMBOLS = [
     "MPIX_Reduce_local_batch", "MPIR_Hip_reduce_batch", "MPIR_Hip_batch_plan_info",
     "MPIX_Reduce_local_strided", "MPIR_Hip_reduce_strided", "MPIR_Hip_strided_plan_info",
     "MPIR_Hip_set_strided_wide_bytes", "MPIR_Hip_strided_test_max_groups",
+    "MPIX_Reduce_local_fetch", "MPIR_Hip_reduce_fetch", "MPIR_Hip_fetch_plan_info",
     # device collectives (include/mpix_hip_coll.h)
     "MPIX_Hip_comm_get_unique_id", "MPIX_Hip_comm_create", "MPIX_Hip_comm_create_loopback",
     "MPIX_Hip_comm_free", "MPIX_Hip_comm_rank", "MPIX_Hip_comm_size",
@@ -193,6 +194,12 @@ def load(path: str | None = None) -> ctypes.CDLL:
     for name in ("MPIR_Hip_set_strided_wide_bytes", "MPIR_Hip_strided_test_max_groups"):
         getattr(lib, name).argtypes = [u64]
         getattr(lib, name).restype = u64
+    lib.MPIX_Reduce_local_fetch.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    lib.MPIX_Reduce_local_fetch.restype = i32
+    lib.MPIR_Hip_reduce_fetch.argtypes = [vp, vp, vp, u64, i32, i32, vp, i32]
+    lib.MPIR_Hip_reduce_fetch.restype = i32
+    lib.MPIR_Hip_fetch_plan_info.argtypes = [vp, vp, vp, u64, i32, i32, ctypes.POINTER(u64)]
+    lib.MPIR_Hip_fetch_plan_info.restype = i32
     lib.MPIX_Hip_comm_get_unique_id.argtypes = [vp]
     lib.MPIX_Hip_comm_get_unique_id.restype = i32
     lib.MPIX_Hip_comm_create.argtypes = [vp, i32, i32, ctypes.POINTER(vp)]
@@ -479,6 +486,35 @@ def strided_plan_info(inbuf: int, in_stride: int, inoutbuf: int, inout_stride: i
         raise LookupError(f"MPIR_Hip_strided_plan_info: {rc}")
     return dict(zip(("form", "launches", "groups", "per", "tile_rows", "elem_rows", "threshold", "rows_per_launch"),
                     (int(v) for v in out)))
+
+
+# ---- fetching reductions (MPIX_Reduce_local_fetch)
+FETCH_EMPTY, FETCH_COPY, FETCH_TILE, FETCH_ELEMS = range(4)
+FETCH_NAMES = ["empty", "copy", "tile", "elems"]
+
+
+def reduce_local_fetch(inbuf: int, inoutbuf: int, fetchbuf: int, count: int, datatype: int, op: int,
+                       stream: int = 0) -> int:
+    """MPIX_Reduce_local_fetch on raw device addresses: fetchbuf receives the bytes
+    inoutbuf held, inoutbuf the combine, in one launch.  MPI_NO_OP and MPI_REPLACE
+    are accepted (inbuf may be 0 under MPI_NO_OP).  stream 0: synchronous on the
+    library stream; otherwise enqueued on that HIP stream, no wait."""
+    return load().MPIX_Reduce_local_fetch(ctypes.c_void_p(inbuf or None), ctypes.c_void_p(inoutbuf or None),
+                                          ctypes.c_void_p(fetchbuf or None), count, datatype, op,
+                                          ctypes.c_void_p(stream or None))
+
+
+def fetch_plan_info(inbuf: int, inoutbuf: int, fetchbuf: int, count: int, datatype: int, op: int) -> dict:
+    """MPIR_Hip_fetch_plan_info: the plan of a fetching reduction of device operands
+    at these addresses (never dereferenced; no GPU needed): path (FETCH_*), groups
+    (the one launch's workgroups; 0 for empty and copy) and the nhead / ntail
+    elements of the tile path.  Raises LookupError where the pair has no kernel."""
+    out = (ctypes.c_uint64 * 4)()
+    rc = load().MPIR_Hip_fetch_plan_info(ctypes.c_void_p(inbuf or None), ctypes.c_void_p(inoutbuf or None),
+                                         ctypes.c_void_p(fetchbuf or None), count, op & 0xFF, _ELEM_BY_HANDLE[datatype], out)
+    if rc:
+        raise LookupError(f"MPIR_Hip_fetch_plan_info: {rc}")
+    return dict(zip(("path", "groups", "nhead", "ntail"), (int(v) for v in out)))
 
 
 MPIX_HIP_ALG_AUTO = 0
