@@ -300,7 +300,8 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_batch(const MPIX_Reduce_local_seg *segs, 
  *       for inbuf == inoutbuf above): the rows run concurrently.
  *   nblocks == 1, or both strides equal to the row's bytes (contiguous rows),
  *       is the single call on nblocks x blocklen elements.
- * Ragged rows, or rows at irregular places, are MPIX_Reduce_local_batch's. */
+ * Equal rows at irregular places are MPIX_Reduce_local_indexed's, ragged rows
+ * MPIX_Reduce_local_batch's. */
 MPICH_API_PUBLIC int MPIX_Reduce_local_strided(const void *inbuf, MPI_Aint in_stride,
                               void *inoutbuf, MPI_Aint inout_stride, int nblocks, int blocklen,
                               MPI_Datatype datatype, MPI_Op op, void *hip_stream);
@@ -351,6 +352,63 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_strided(const void *inbuf, MPI_Aint in_st
  *       captured into a HIP graph. */
 MPICH_API_PUBLIC int MPIX_Reduce_local_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, int count,
                             MPI_Datatype datatype, MPI_Op op, void *hip_stream);
+/* Indexed local reduction: equal blocks at the places a displacement table
+ * names, in one launch -- the target of an accumulate on an
+ * MPI_Type_create_indexed_block / hindexed_block type (a scatter-add: embedding
+ * row gradients, sparse updates), or the gather-reduce the other way round.
+ * For k in [0, nblocks):
+ *   MPI_Reduce_local((char *) inbuf + in_off(k), (char *) inoutbuf + io_off(k),
+ *                    blocklen, datatype, op)
+ * every block bit-identical to that call; no byte outside the blocks is read or
+ * written.  X_off(k) = X_displs[k] * disp_unit bytes where the table is given,
+ * k * blocklen * the datatype's size where it is NULL (a packed operand).
+ *   disp_unit 1 is hindexed_block (byte displacements), the type's extent
+ *       indexed_block, a row's bytes makes the table row indices.  in_displs
+ *       NULL with inout_displs given is the scatter (the accumulate target),
+ *       the reverse the gather; both may be given.  Both NULL is the single
+ *       call on nblocks x blocklen elements.
+ *   Displacements may be negative.  A repeated in_displs entry is fine (input
+ *       is only read).  Output blocks that overlap each other, or an input
+ *       block, are undefined and not checked: MPI forbids overlapping target
+ *       entries in an accumulate, and the blocks run concurrently.
+ *   Ops and types as the strided call validates them, in its order: MPI_REPLACE,
+ *       MPI_NO_OP, null, invalid and user ops, and MPI_LAND / MPI_LOR on
+ *       floating types: MPI_ERR_OP; nblocks < 0 or blocklen < 0: MPI_ERR_COUNT;
+ *       MPI_IN_PLACE: MPI_ERR_BUFFER; inbuf == inoutbuf: MPI_ERR_BUFFER under
+ *       MPIR_CVAR_COLL_ALIAS_CHECK; disp_unit <= 0: MPI_ERR_ARG.  Either count 0
+ *       succeeds, and no pointer is looked at, the tables included; the op and
+ *       disp_unit are still checked then, as the strided call still checks its
+ *       op and the sign of its strides.
+ *   Both base pointers must be device memory on one device (MPI_ERR_BUFFER).
+ *       A table may be device memory on that device: the kernel reads it, and
+ *       it must stay unchanged until the work completes.  With hip_stream NULL
+ *       a table may also be host memory: the library copies it to a buffer of
+ *       its own ahead of the kernel, and, reading it anyway, checks every
+ *       displs[k] * disp_unit for overflow (MPI_ERR_ARG) and that the lowest
+ *       block's first byte and the highest block's last byte are device memory
+ *       (MPI_ERR_BUFFER).  A host table with a stream is MPI_ERR_BUFFER.
+ *   hip_stream NULL: synchronous, every block complete on return; otherwise
+ *       enqueued on that stream without waiting; with device tables everything
+ *       else travels in the kernel arguments, so the call can be captured into
+ *       a graph.
+ *   Everything is validated and classified before the first launch: a call
+ *       that returns an error has modified nothing.
+ *   Blocks shorter than the strided call's wide threshold move as 16-byte
+ *       vectors only where the library can tell without reading a table that
+ *       every address is a multiple of 16: blocklen x size and both bases
+ *       multiples of 16, and disp_unit a multiple of 16.  Callers with 16-byte
+ *       aligned blocks should pass disp_unit 16 (or a multiple) and scale the
+ *       displacements, not byte displacements with disp_unit 1, which move
+ *       element by element.
+ * Ragged blocks (MPI_Type_indexed proper) stay with MPIX_Reduce_local_batch;
+ * over the same equal blocks this call was measured a little behind it at two
+ * blocks (by the spread between runs) and ahead from eight on.  Blocks at a constant stride are
+ * MPIX_Reduce_local_strided's: it reads no table and plans its grid exactly, and
+ * takes somewhat less time on the same operands (Indexed reductions,
+ * has the figures for both). */
+MPICH_API_PUBLIC int MPIX_Reduce_local_indexed(const void *inbuf, const MPI_Aint * in_displs,
+                              void *inoutbuf, const MPI_Aint * inout_displs, MPI_Aint disp_unit,
+                              int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream);
 MPICH_API_PUBLIC int MPIX_Reduce_local_set_errhandler(MPI_Errhandler errhandler);
 MPICH_API_PUBLIC int MPIX_Reduce_local_get_errhandler(MPI_Errhandler * errhandler);
 

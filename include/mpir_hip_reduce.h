@@ -56,7 +56,7 @@ enum MPIR_Hip_elem {
 #define MPIR_HIP_ERUNTIME  2   /* HIP runtime failure; see MPIR_Hip_error_string() */
 #define MPIR_HIP_ENOKERNEL 3   /* (op, elem) pair has no kernel */
 #define MPIR_HIP_ENODEV    4   /* no usable GPU */
-#define MPIR_HIP_EARG      5   /* an argument out of range (MPIR_Hip_reduce_strided's strides) */
+#define MPIR_HIP_EARG      5   /* an argument out of range (MPIR_Hip_reduce_strided's strides, MPIR_Hip_reduce_indexed's disp_unit and offsets) */
 
 /* Combine inoutbuf[i] = op(inoutbuf[i], inbuf[i]) for i < count elements of
  * class `elem`.  Pointers may be device, pinned-host or pageable-host memory
@@ -230,6 +230,68 @@ int MPIR_Hip_reduce_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, uin
 #define MPIR_HIP_FETCH_ELEMS 3   /* any other alignment, and the 32-byte classes: element runs */
 int MPIR_Hip_fetch_plan_info(const void *inbuf, const void *inoutbuf, const void *fetchbuf, uint64_t count, int op,
                              int elem, uint64_t out[4]);
+
+/* Indexed reduction: for k < nblocks, io_k[i] = op(io_k[i], in_k[i]), i <
+ * blocklen, where in_k = inbuf + in_displs[k] * disp_unit and io_k = inoutbuf +
+ * io_displs[k] * disp_unit bytes (signed displacements); a side whose table is
+ * NULL is packed, block k at k * blocklen * the element's size.  The blocks of
+ * an MPI_Type_create_indexed_block / hindexed_block operand under one (op,
+ * elem) -- a scatter-add with io_displs, a gather-reduce with in_displs -- in
+ * one kernel launch however many blocks there are (further launches on the
+ * same stream take later block ranges, their table pointers and packed bases
+ * advanced, once a launch would pass MPIR_HIP_BATCH_MAX_GROUPS workgroups).
+ * Each block's result is bit-identical to MPIR_Hip_reduce on it; no byte outside
+ * the blocks is read or written.  Output blocks that overlap each other or an
+ * input block are undefined (not checked: the blocks run concurrently); a
+ * repeated in_displs entry is fine.
+ * disp_unit == 0, or more than INT64_MAX, is MPIR_HIP_EARG, whatever the
+ * counts (MPIX_Reduce_local_indexed answers MPI_ERR_ARG likewise).  Otherwise
+ * nblocks == 0 or blocklen == 0 succeeds with no pointer looked at, tables
+ * included.  Both
+ * tables NULL is MPIR_Hip_reduce on nblocks * blocklen elements.
+ * Residency: both bases must be device memory on one device, and the first and
+ * the last byte of a packed side's span (else MPIR_HIP_EBUFFER).  A table is
+ * device memory on that device, read by the kernel: it must stay unchanged until
+ * the work completes.  With sync != 0 and hip_stream NULL a table may be host
+ * memory instead: it is copied into a per-(thread, device) table buffer of the
+ * library's, stream-ordered ahead of the kernel; as the library reads such a
+ * table anyway, it also checks displs[k] * disp_unit for overflow
+ * (MPIR_HIP_EARG) and classifies the first byte of the lowest block and the
+ * last byte of the highest.  A host table in any other call is
+ * MPIR_HIP_EBUFFER.  Everything is classified before the first launch, so a
+ * call that fails has written nothing.  With device tables the launch carries
+ * everything else in its kernel arguments (graph-capturable).
+ * The wide / narrow threshold is the strided call's
+ * (MPIR_Hip_set_strided_wide_bytes), and so are the per-launch workgroup cap
+ * and its test hook (MPIR_Hip_strided_test_max_groups).
+ * Narrow blocks move as 16-byte vectors only where every address is provably a
+ * multiple of 16 without reading a table: blocklen * size and both bases
+ * multiples of 16, and disp_unit a multiple of 16 for each side with a table.
+ * A caller whose blocks are 16-byte aligned should therefore pass disp_unit 16
+ * (or a multiple) with displacements scaled to it, not byte displacements with
+ * disp_unit 1, which take the element form.
+ * MPIR_HIP_ENOKERNEL for REPLACE and pairs with no kernel. */
+int MPIR_Hip_reduce_indexed(const void *inbuf, const int64_t *in_displs, void *inoutbuf, const int64_t *io_displs,
+                            uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen, int op, int elem,
+                            void *hip_stream, int sync);
+
+/* For tests and tools: the launches MPIR_Hip_reduce_indexed would make for
+ * device operands and tables at these addresses, from the same planner the
+ * launch runs (host arithmetic on the pointer values only: the tables are never
+ * read, only compared with NULL; no GPU is needed).  out = {form, launches,
+ * workgroups over all launches, G (WIDE: workgroups per block, the most a block
+ * can need at any address) or units per workgroup (NARROW), the wide / narrow
+ * threshold in force (bytes), blocks per launch}.  SINGLE reports
+ * MPIR_Hip_plan_info's grid as its workgroups.  Returns as
+ * MPIR_Hip_reduce_indexed does for the same arguments, residency apart. */
+#define MPIR_HIP_INDEXED_EMPTY        0   /* nblocks or blocklen 0: nothing to do */
+#define MPIR_HIP_INDEXED_SINGLE       1   /* both tables NULL: MPIR_Hip_reduce's own plan */
+#define MPIR_HIP_INDEXED_WIDE         2   /* block bytes >= the threshold: nblocks x G workgroups, the batch's segment code */
+#define MPIR_HIP_INDEXED_NARROW_VEC   3   /* flattened 16-byte units: every address provably a multiple of 16 */
+#define MPIR_HIP_INDEXED_NARROW_ELEMS 4   /* flattened elements, any alignment */
+int MPIR_Hip_indexed_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
+                               const int64_t *io_displs, uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen,
+                               int op, int elem, uint64_t out[6]);
 
 /* Flags for the calling thread's later MPIR_Hip_combine calls; returns the
  * previous flags.  MPIR_HIP_COMBINE_UNCAPPED: the fused folds run without the

@@ -31,6 +31,7 @@ Entry g_table[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 
 // Strided rows of at least this many bytes take the wide form (one row's tiles
@@ -634,6 +635,104 @@ void strided_launches(const StridedPlan &p, const void *in, uint64_t in_stride, 
     }
 }
 
+// ---- indexed calls: the strided call's plan with a table where the stride was.
+// The forms carry the strided call's numbers, so StridedPlan and
+// strided_launch_groups serve both.
+static_assert(MPIR_HIP_INDEXED_EMPTY == MPIR_HIP_STRIDED_EMPTY && MPIR_HIP_INDEXED_SINGLE == MPIR_HIP_STRIDED_SINGLE &&
+                  MPIR_HIP_INDEXED_WIDE == MPIR_HIP_STRIDED_WIDE &&
+                  MPIR_HIP_INDEXED_NARROW_VEC == MPIR_HIP_STRIDED_NARROW_VEC &&
+                  MPIR_HIP_INDEXED_NARROW_ELEMS == MPIR_HIP_STRIDED_NARROW_ELEMS,
+              "the indexed forms are the strided forms");
+
+// the argument checks MPIR_Hip_reduce_indexed makes before it looks at a
+// pointer; MPIR_HIP_OK with *form EMPTY or SINGLE where that settles the call
+int indexed_args(const void *in_displs, const void *io_displs, uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen,
+                 int op, int elem, int *form) {
+    if (!pair_in_range(op, elem) || !g_indexed[op][elem].launch || !g_batch[op][elem].groups) return MPIR_HIP_ENOKERNEL;
+    // (before the counts, as the MPIX entry checks it: the two layers answer alike)
+    if (!disp_unit || disp_unit > (~(uint64_t)0 >> 1)) return MPIR_HIP_EARG;
+    *form = MPIR_HIP_INDEXED_EMPTY;
+    if (!nblocks || !blocklen) return MPIR_HIP_OK;
+    const uint64_t esz = g_elem_size[elem];
+    if (blocklen > (~(uint64_t)0 >> 1) / esz) return MPIR_HIP_EARG;
+    // a packed side's span, and the single call's count
+    if (nblocks > (~(uint64_t)0 >> 1) / (blocklen * esz)) return MPIR_HIP_EARG;
+    *form = !in_displs && !io_displs ? MPIR_HIP_INDEXED_SINGLE : MPIR_HIP_INDEXED_WIDE;
+    return MPIR_HIP_OK;
+}
+
+// (for a call indexed_args left as WIDE: at least one table).  The tables are
+// compared with null, never read: what a device table holds the host cannot see,
+// so G is the worst case and the vector form needs disp_unit's word for it.
+void indexed_plan(const void *in, const void *in_displs, const void *io, const void *io_displs, uint64_t disp_unit,
+                  uint64_t nblocks, uint64_t blocklen, int elem, StridedPlan &p) {
+    const uint64_t esz = g_elem_size[elem];
+    const uint64_t cap = t_strided_cap && t_strided_cap < kBatchMaxGroups ? t_strided_cap : kBatchMaxGroups;
+    p.row_bytes = blocklen * esz;
+    p.threshold = g_strided_wide.load(std::memory_order_relaxed);
+    if (p.row_bytes >= p.threshold) {
+        p.form = MPIR_HIP_INDEXED_WIDE;
+        p.per = indexed_row_groups_max(p.row_bytes, esz);
+        p.upr = 0;
+        p.rows_per_launch = cap / p.per;                // a block is never split between launches
+    } else {
+        const uint64_t all = p.row_bytes | reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(io) |
+                             (in_displs || io_displs ? disp_unit : 0);
+        const bool vec = esz <= 16 && (all & 15) == 0;
+        const uint64_t unit = vec ? 16 : esz;
+        p.form = vec ? MPIR_HIP_INDEXED_NARROW_VEC : MPIR_HIP_INDEXED_NARROW_ELEMS;
+        p.per = kTileBytes / unit;
+        p.upr = p.row_bytes / unit;
+        // the kernel's per-lane division is 32-bit: a launch's blocks stay below 2^32
+        p.rows_per_launch = std::min<uint64_t>(cap * p.per / p.upr, 0xFFFFFFFFull);
+    }
+    p.rows_per_launch = std::min(std::max<uint64_t>(p.rows_per_launch, 1), nblocks);
+    const uint64_t full = nblocks / p.rows_per_launch, rest = nblocks % p.rows_per_launch;
+    p.launches = full + (rest != 0);
+    p.groups = full * strided_launch_groups(p, p.rows_per_launch) + (rest ? strided_launch_groups(p, rest) : 0);
+}
+
+// The launches of a plan: later block ranges, the table pointers advanced by
+// the blocks before them and a packed side's base by those blocks' bytes.
+// emit(args, groups) per launch, until it returns false.
+template <class F>
+void indexed_launches(const StridedPlan &p, const void *in, const int64_t *in_displs, void *io,
+                      const int64_t *io_displs, uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen, F emit) {
+    for (uint64_t row0 = 0; row0 < nblocks; row0 += p.rows_per_launch) {
+        const uint64_t n = std::min(p.rows_per_launch, nblocks - row0);
+        const IndexedArgs a{static_cast<const char *>(in) + (in_displs ? 0 : row0 * p.row_bytes),
+                            static_cast<char *>(io) + (io_displs ? 0 : row0 * p.row_bytes),
+                            in_displs ? in_displs + row0 : nullptr, io_displs ? io_displs + row0 : nullptr,
+                            disp_unit, blocklen, (uint32_t)n, (uint32_t)p.form,
+                            (uint32_t)(p.form == MPIR_HIP_INDEXED_WIDE ? p.per : p.upr), 0};
+        if (!emit(a, strided_launch_groups(p, n))) return;
+    }
+}
+
+// A host displacement table, read before anything is enqueued: every
+// displs[k] * disp_unit must fit 64 signed bits (MPIR_HIP_EARG), and the first
+// byte of the lowest block and the last byte of the highest must be device
+// memory on `dev` (MPIR_HIP_EBUFFER).
+int indexed_host_table(const char *base, const int64_t *displs, uint64_t disp_unit, uint64_t nblocks,
+                       uint64_t row_bytes, int dev) {
+    int64_t lo = displs[0], hi = displs[0];
+    for (uint64_t k = 1; k < nblocks; ++k) {
+        lo = std::min(lo, displs[k]);
+        hi = std::max(hi, displs[k]);
+    }
+    int64_t off_lo, off_hi;
+    if (__builtin_mul_overflow(lo, (int64_t)disp_unit, &off_lo) || __builtin_mul_overflow(hi, (int64_t)disp_unit, &off_hi))
+        return MPIR_HIP_EARG;
+    if (off_hi > (int64_t)((~(uint64_t)0 >> 1) - row_bytes)) return MPIR_HIP_EARG;
+    const void *ends[2] = {base + off_lo, base + off_hi + (row_bytes - 1)};
+    DeviceSpan span;
+    for (int k = 0; k < 2; ++k) {
+        int d = -1;
+        if (classify_in_span(ends[k], &d, span) != LOC_DEVICE || d != dev) return MPIR_HIP_EBUFFER;
+    }
+    return MPIR_HIP_OK;
+}
+
 // the argument checks MPIR_Hip_reduce_fetch makes before it looks at a pointer;
 // MPIR_HIP_OK with *path EMPTY or COPY where that settles the call, else TILE
 // (the plan then says which of the kernel's two paths)
@@ -1074,6 +1173,131 @@ int MPIR_Hip_reduce_strided(const void *inbuf, uint64_t in_stride, void *inoutbu
         if (e != hipSuccess) rc = set_err(e, "strided launch");
         else if (sync) rc = wait_stream(dev, s);
     }
+    return rc;
+}
+
+int MPIR_Hip_indexed_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
+                               const int64_t *io_displs, uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen,
+                               int op, int elem, uint64_t out[6]) {
+    int form = 0;
+    const int rc = indexed_args(in_displs, io_displs, disp_unit, nblocks, blocklen, op, elem, &form);
+    if (rc != MPIR_HIP_OK) return rc;
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    out[0] = (uint64_t)form;
+    out[4] = mpir_hip::g_strided_wide.load(std::memory_order_relaxed);
+    if (form == MPIR_HIP_INDEXED_EMPTY) return MPIR_HIP_OK;
+    if (form == MPIR_HIP_INDEXED_SINGLE) {
+        // the single call's own plan (MPIR_Hip_plan_info)
+        const plan_fn fn = g_table[op][elem].plan ? g_table[op][elem].plan : g_table[op][elem].wide;
+        if (!fn) return MPIR_HIP_ENOKERNEL;
+        ReducePlan p;
+        fn(inbuf, const_cast<void *>(inoutbuf), nblocks * blocklen, &p);
+        out[1] = 1;
+        out[2] = p.groups;
+        out[5] = nblocks;
+        return MPIR_HIP_OK;
+    }
+    StridedPlan p;
+    indexed_plan(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, elem, p);
+    out[0] = (uint64_t)p.form;
+    out[1] = p.launches;
+    out[2] = p.groups;
+    out[3] = p.per;
+    out[5] = p.rows_per_launch;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_reduce_indexed(const void *inbuf, const int64_t *in_displs, void *inoutbuf, const int64_t *io_displs,
+                            uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen, int op, int elem,
+                            void *hip_stream, int sync) {
+    int form = 0;
+    int rc = indexed_args(in_displs, io_displs, disp_unit, nblocks, blocklen, op, elem, &form);
+    if (rc != MPIR_HIP_OK || form == MPIR_HIP_INDEXED_EMPTY) return rc;
+    ctx().err[0] = 0;
+    // everything the call can classify, before anything is enqueued (a call that
+    // fails has written nothing): both bases; the last byte of a packed side;
+    // each table -- device memory on the operands' device, both its ends, or, in a
+    // synchronous call on the library stream, host memory, which is then read for
+    // the blocks' extremes
+    const uint64_t row_bytes = blocklen * g_elem_size[elem];
+    const char *in = static_cast<const char *>(inbuf);
+    char *io = static_cast<char *>(inoutbuf);
+    const int64_t *displs[2] = {in_displs, io_displs};
+    const char *base[2] = {in, io};
+    bool host_table[2] = {false, false};
+    int dev = -1;
+    DeviceSpan span[2];
+    for (int k = 0; k < 2; ++k) {
+        int d = -1;
+        if (classify_in_span(base[k], &d, span[k]) != LOC_DEVICE || (k && d != dev)) return MPIR_HIP_EBUFFER;
+        dev = d;
+        if (!displs[k] &&
+            (classify_in_span(base[k] + (nblocks * row_bytes - 1), &d, span[k]) != LOC_DEVICE || d != dev))
+            return MPIR_HIP_EBUFFER;
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (!displs[k]) continue;
+        DeviceSpan ts;
+        int d = -1;
+        const Loc first = classify_in_span(displs[k], &d, ts);
+        if (first == LOC_DEVICE) {
+            int d2 = -1;
+            if (d != dev ||
+                classify_in_span(reinterpret_cast<const char *>(displs[k] + nblocks) - 1, &d2, ts) != LOC_DEVICE ||
+                d2 != dev)
+                return MPIR_HIP_EBUFFER;
+            continue;
+        }
+        if (hip_stream || !sync) return MPIR_HIP_EBUFFER;       // a host table would be read after the call returned
+        host_table[k] = true;
+        rc = indexed_host_table(base[k], displs[k], disp_unit, nblocks, row_bytes, dev);
+        if (rc != MPIR_HIP_OK) return rc;
+    }
+    // both tables NULL: the single call -- the direct AQL dispatch when
+    // synchronous, every existing plan
+    if (form == MPIR_HIP_INDEXED_SINGLE)
+        return MPIR_Hip_reduce(inbuf, inoutbuf, nblocks * blocklen, op, elem, hip_stream, sync);
+    StridedPlan p;
+    indexed_plan(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, elem, p);
+    if (p.form == MPIR_HIP_INDEXED_WIDE && p.per > kBatchMaxGroups) {
+        snprintf(ctx().err, sizeof(ctx().err), "an indexed block needs more workgroups than one launch holds");
+        return MPIR_HIP_ERUNTIME;
+    }
+    DeviceScope on(dev);
+    if (!on.ok()) return on.err();
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!s) rc = get_stream(dev, S_MAIN, &s);
+    if (rc != MPIR_HIP_OK) return rc;
+    if (host_table[0] || host_table[1]) {
+        // host tables into the thread's table buffer, stream-ordered ahead of the
+        // kernels (the earlier synchronous call that read the buffer has returned)
+        const size_t tbytes = (size_t)nblocks * sizeof(int64_t);
+        char *buf = nullptr;
+        rc = get_tables(dev, tbytes * ((size_t)host_table[0] + (size_t)host_table[1]), &buf);
+        if (rc != MPIR_HIP_OK) return rc;               // (nothing of this call is queued yet)
+        for (int k = 0; k < 2; ++k) {
+            if (!host_table[k]) continue;
+            const hipError_t ce = hipMemcpyAsync(buf, displs[k], tbytes, hipMemcpyHostToDevice, s);
+            if (ce != hipSuccess) {
+                // (the other table's copy may be queued on the library stream)
+                ctx().dev[dev].main_pending = true;
+                return set_err(ce, "indexed table copy");
+            }
+            displs[k] = reinterpret_cast<const int64_t *>(buf);
+            buf += tbytes;
+        }
+    }
+    hipError_t e = hipSuccess;
+    const indexed_fn launch = g_indexed[op][elem].launch;
+    indexed_launches(p, inbuf, displs[0], inoutbuf, displs[1], disp_unit, nblocks, blocklen,
+                     [&](const IndexedArgs &a, uint64_t groups) {
+                         e = launch(&a, groups, s);
+                         return e == hipSuccess;
+                     });
+    // (launches made before one that failed are still queued on the library stream)
+    if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
+    if (e != hipSuccess) rc = set_err(e, "indexed launch");
+    else if (sync) rc = wait_stream(dev, s);
     return rc;
 }
 

@@ -35,6 +35,7 @@ typedef hipError_t (*batch_fn)(const BatchArgs *, uint64_t, hipStream_t);
 typedef uint64_t (*bgroups_fn)(const void *, const void *, uint64_t, int *);
 typedef hipError_t (*strided_fn)(const StridedArgs *, uint64_t, hipStream_t);
 typedef hipError_t (*fetch_fn)(const FetchArgs *, hipStream_t);
+typedef hipError_t (*indexed_fn)(const IndexedArgs *, uint64_t, hipStream_t);
 typedef void (*fplan_fn)(const FetchArgs *, FetchPlan *);
 
 // plan: plan_reduce<T> (reduce_kernels.hpp) for the classes whose launcher is
@@ -62,6 +63,10 @@ struct StridedEntry { strided_fn launch; };
 // that launch makes, for MPIR_Hip_fetch_plan_info.  MPI_NO_OP and MPI_REPLACE
 // are device copies and have no entry.
 struct FetchEntry { fetch_fn launch; fplan_fn plan; };
+// g_indexed[op][elem], likewise: launch_indexed<Op, T>, one launch of
+// k_reduce_indexed over a range of blocks (MPIR_Hip_reduce_indexed), for the
+// pairs g_batch holds (reg_indexed<>, from the reg_indexed_*.hip units).
+struct IndexedEntry { indexed_fn launch; };
 
 // float / double SUM and PROD on the host: the SSE instruction itself.  The
 // reference's loop `a[i] = a[i] + b[i]` (opsum.c:21-76, gcc -O2) is an
@@ -132,6 +137,7 @@ extern Entry g_table[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 constexpr int kMultiMaxP = 8;
 extern multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 
@@ -165,6 +171,11 @@ void reg_strided(int op, int elem) {
 template <class Op, class T>
 void reg_fetch(int op, int elem) {
     g_fetch[op][elem] = FetchEntry{&launch_fetch<Op, T>, &fetch_plan<T>};
+}
+// the indexed kernel of the same pairs, from the reg_indexed_*.hip units
+template <class Op, class T>
+void reg_indexed(int op, int elem) {
+    g_indexed[op][elem] = IndexedEntry{&launch_indexed<Op, T>};
 }
 template <class Op, class T>
 void reg_multi(int op, int elem) {

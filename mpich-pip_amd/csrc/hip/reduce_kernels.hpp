@@ -922,6 +922,175 @@ hipError_t launch_strided(const StridedArgs *a, uint64_t groups, hipStream_t s) 
 }
 
 // ============================================================================
+// Indexed reductions (MPIR_Hip_reduce_indexed): nrows equal blocks of blocklen
+// elements, block k at in + in_displs[k] * disp_unit and io + io_displs[k] *
+// disp_unit (signed displacements, device tables), a side with no table packed
+// (block k at k * the block's bytes).  The target of an accumulate on an
+// MPI_Type_create_indexed_block / hindexed_block type -- a scatter-add, or the
+// gather the other way round.  It is the strided kernel with a block's byte
+// offset read from a table instead of computed as row * stride, so any number
+// of blocks is one launch (up to kBatchMaxGroups workgroups) with 64 bytes of
+// kernel arguments; the forms are the strided kernel's:
+//
+//   * WIDE: the grid is nrows x G.  The host cannot read a device table, so G
+//     is the most workgroups a block can need at any address
+//     (indexed_row_groups_max), never the on-grid count.  Workgroup wg takes
+//     block wg / G: it loads that block's displacements from an address formed
+//     from the kernel arguments and blockIdx alone, passes their halves through
+//     readfirstlane so that the block's pointers are wave-uniform to the
+//     compiler too (reduce_tile's buffer descriptors stay in scalar registers,
+//     no waterfall loop), and runs reduce_seg with tile wg % G.
+//   * NARROW: the blocks flattened into units as the strided kernel flattens
+//     rows, one 64-bit division per workgroup and a 32-bit one per lane; a lane
+//     then loads its blocks' displacements.  A unit is a 16-byte vector only
+//     when the host can prove every address a multiple of 16 without reading
+//     the table: block bytes and both bases multiples of 16, and disp_unit a
+//     multiple of 16 for each side that has a table; else one element through
+//     batch_elem_at.  In the vector form a side's four table loads are one
+//     straight run (the null tests are outside the unrolled loops, a unit past
+//     the last block is clamped into it instead of branched around), so a lane
+//     waits one memory round trip per side with a table before its data loads,
+//     which again issue together.  The element form loads a displacement per
+//     element and waits for it: one more round trip in each iteration.
+//
+// No LDS, no scratch, no gridDim.  Tile and vector stores are nt; element
+// stores are batch_elem_at's plain stores, as in the batch and the strided call.
+// ============================================================================
+struct IndexedArgs {
+    const char *in;             // the bases; of a packed side, block 0 of this launch
+    char *io;
+    const int64_t *in_displs;   // entry 0 is this launch's first block; null: packed
+    const int64_t *io_displs;
+    uint64_t disp_unit;         // bytes per displacement unit, > 0
+    uint64_t blocklen;          // elements per block, > 0
+    uint32_t nrows;             // blocks of this launch, > 0
+    uint32_t form;              // MPIR_HIP_INDEXED_WIDE / _NARROW_VEC / _NARROW_ELEMS
+    uint32_t per;               // WIDE: G, workgroups per block; NARROW: units per block
+    uint32_t pad_;
+};
+
+// G of the wide form: strided_row_groups_max with no promise about where a
+// block's inoutbuf address falls on the 16 KiB grid
+inline uint64_t indexed_row_groups_max(uint64_t row_bytes, size_t esz) {
+    return strided_row_groups_max(row_bytes, esz, reinterpret_cast<const void *>((uintptr_t)16), 0);
+}
+
+// byte offset of block `row`: the table's entry times disp_unit (the product
+// wraps as pointer arithmetic does: displacements are signed), or the packed place
+__device__ __forceinline__ uint64_t indexed_off(const int64_t *displs, uint64_t row, uint64_t disp_unit,
+                                                uint64_t row_bytes) {
+    return displs ? (uint64_t)displs[row] * disp_unit : row * row_bytes;
+}
+
+// a 16-byte vector in the global address space: the narrow vector form's
+// per-lane accesses are global_load / global_store, not flat
+typedef u32x4 __attribute__((address_space(1))) global_u32x4;
+
+template <class Op, class T>
+__device__ __forceinline__ void reduce_indexed_narrow(const IndexedArgs &a) {
+    const uint32_t upr = a.per;                             // units per block
+    const uint64_t row_bytes = a.blocklen * sizeof(T);
+    const unsigned t = threadIdx.x;
+    if constexpr (sizeof(T) <= 16) {
+        if (a.form == MPIR_HIP_INDEXED_NARROW_VEC) {
+            constexpr uint32_t upw = strided_units_per_group<T>(true);
+            constexpr int per_lane = (int)(upw / kThreads);
+            const uint64_t u0 = (uint64_t)blockIdx.x * upw;
+            const uint64_t row0 = u0 / upr;
+            const uint32_t col0 = (uint32_t)(u0 - row0 * upr);
+            // A unit past the launch's last block is clamped into that block: its
+            // table and data loads stay inside the operands and need no branch, so
+            // each batch of loads issues back to back; only the store is guarded.
+            // (The workgroup's first unit is always a real one: nrows > row0.)
+            const uint64_t last = a.nrows - 1;
+            u32x4 x[per_lane], y[per_lane];
+            uint64_t row[per_lane], off[per_lane], oi[per_lane], oo[per_lane];
+            bool ok[per_lane];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                const uint32_t c = col0 + t + (uint32_t)j * kThreads;
+                const uint32_t q = c / upr;
+                const uint64_t r = row0 + q;
+                ok[j] = r <= last;
+                row[j] = ok[j] ? r : last;
+                off[j] = (uint64_t)(c - q * upr) * 16;
+                oi[j] = oo[j] = row[j] * row_bytes;         // the packed place
+            }
+            // the null tests are uniform and outside the unrolled loops: a side's
+            // per_lane table loads are one straight run
+            if (a.io_displs) {
+                int64_t d[per_lane];
+#pragma unroll
+                for (int j = 0; j < per_lane; ++j) d[j] = a.io_displs[row[j]];
+#pragma unroll
+                for (int j = 0; j < per_lane; ++j) oo[j] = (uint64_t)d[j] * a.disp_unit;
+            }
+            if (a.in_displs) {
+                int64_t d[per_lane];
+#pragma unroll
+                for (int j = 0; j < per_lane; ++j) d[j] = a.in_displs[row[j]];
+#pragma unroll
+                for (int j = 0; j < per_lane; ++j) oi[j] = (uint64_t)d[j] * a.disp_unit;
+            }
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                x[j] = __builtin_nontemporal_load((const global_u32x4 *)(a.io + oo[j] + off[j]));
+                y[j] = __builtin_nontemporal_load((const global_u32x4 *)(a.in + oi[j] + off[j]));
+            }
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j)
+                if (ok[j])
+                    __builtin_nontemporal_store(combine16<Op, T>(x[j], y[j]),
+                                                (global_u32x4 *)(a.io + oo[j] + off[j]));
+            return;
+        }
+    }
+    constexpr uint32_t upw = strided_units_per_group<T>(false);
+    const uint64_t u0 = (uint64_t)blockIdx.x * upw;
+    const uint64_t row0 = u0 / upr;
+    const uint32_t col0 = (uint32_t)(u0 - row0 * upr);
+    for (uint32_t k = t; k < upw; k += kThreads) {
+        const uint32_t c = col0 + k;
+        const uint32_t q = c / upr;
+        const uint64_t row = row0 + q;
+        if (row >= a.nrows) break;                          // blocks only grow with k
+        batch_elem_at<Op, T>(a.in + indexed_off(a.in_displs, row, a.disp_unit, row_bytes),
+                             a.io + indexed_off(a.io_displs, row, a.disp_unit, row_bytes), c - q * upr);
+    }
+}
+
+// a 64-bit value every lane of the wave holds, made provably so
+__device__ __forceinline__ uint64_t wave_uniform64(uint64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_reduce_indexed(IndexedArgs a) {
+    if (a.form == MPIR_HIP_INDEXED_WIDE) {
+        const uint32_t row = blockIdx.x / a.per;
+        if (row >= a.nrows) return;
+        const uint64_t row_bytes = a.blocklen * sizeof(T);
+        const uint64_t oi = wave_uniform64(indexed_off(a.in_displs, row, a.disp_unit, row_bytes));
+        const uint64_t oo = wave_uniform64(indexed_off(a.io_displs, row, a.disp_unit, row_bytes));
+        reduce_seg<Op, T>(a.in + oi, a.io + oo, a.blocklen, blockIdx.x - row * a.per);
+        return;
+    }
+    reduce_indexed_narrow<Op, T>(a);
+}
+
+// one launch: `groups` workgroups over a.nrows blocks (the planner's count, as
+// for launch_strided)
+template <class Op, class T>
+hipError_t launch_indexed(const IndexedArgs *a, uint64_t groups, hipStream_t s) {
+    if (!a->nrows || !a->per || !a->blocklen || !a->disp_unit || groups < 1 || groups > kBatchMaxGroups)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_reduce_indexed<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+// ============================================================================
 // Fetching reductions (MPIR_Hip_reduce_fetch): fetch[i] = the bytes io[i] held,
 // io[i] = op(io[i], in[i]), in ONE pass -- the target side of MPI_Get_accumulate
 // and MPI_Fetch_and_op, which copies the target's old contents into the response

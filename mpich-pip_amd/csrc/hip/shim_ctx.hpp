@@ -47,6 +47,8 @@ struct DevCtx {
     size_t bounce_bytes = 0;
     char *zc = nullptr;          // pinned, device-mapped slot for small mixed-residency calls
     size_t zc_bytes = 0;
+    char *tables = nullptr;      // device copy of a synchronous indexed call's host displacement tables
+    size_t tables_bytes = 0;
 };
 
 // HIP's verdict on host pages the HSA query does not know (classify below)
@@ -205,6 +207,25 @@ inline int get_zc(int dev, size_t bytes, char **out) {
         d.zc_bytes = want;
     }
     *out = d.zc;
+    return MPIR_HIP_OK;
+}
+
+// the calling thread's displacement-table buffer on `dev` (MPIR_Hip_reduce_indexed's
+// host tables).  Not `scratch`: stream-variant work may still be reading that,
+// while this buffer's only readers are synchronous calls, complete when they
+// returned -- but for one that failed after it enqueued, hence the wait.
+inline int get_tables(int dev, size_t bytes, char **out) {
+    DevCtx &d = ctx().dev[dev];
+    if (d.tables_bytes < bytes) {
+        if (d.tables) HIPCHK(hipDeviceSynchronize());
+        if (d.tables) HIPCHK(hipFree(d.tables));
+        d.tables = nullptr;
+        d.tables_bytes = 0;
+        const size_t want = bytes < ((size_t)64 << 10) ? ((size_t)64 << 10) : bytes;
+        HIPCHK(hipMalloc(&d.tables, want));
+        d.tables_bytes = want;
+    }
+    *out = d.tables;
     return MPIR_HIP_OK;
 }
 

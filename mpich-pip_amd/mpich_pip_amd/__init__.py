@@ -115,6 +115,7 @@ EXPORTED_SYMBOLS = [
     "MPIX_Reduce_local_strided", "MPIR_Hip_reduce_strided", "MPIR_Hip_strided_plan_info",
     "MPIR_Hip_set_strided_wide_bytes", "MPIR_Hip_strided_test_max_groups",
     "MPIX_Reduce_local_fetch", "MPIR_Hip_reduce_fetch", "MPIR_Hip_fetch_plan_info",
+    "MPIX_Reduce_local_indexed", "MPIR_Hip_reduce_indexed", "MPIR_Hip_indexed_plan_info",
     # device collectives (include/mpix_hip_coll.h)
     "MPIX_Hip_comm_get_unique_id", "MPIX_Hip_comm_create", "MPIX_Hip_comm_create_loopback",
     "MPIX_Hip_comm_free", "MPIX_Hip_comm_rank", "MPIX_Hip_comm_size",
@@ -200,6 +201,12 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.MPIR_Hip_reduce_fetch.restype = i32
     lib.MPIR_Hip_fetch_plan_info.argtypes = [vp, vp, vp, u64, i32, i32, ctypes.POINTER(u64)]
     lib.MPIR_Hip_fetch_plan_info.restype = i32
+    lib.MPIX_Reduce_local_indexed.argtypes = [vp, vp, vp, vp, ctypes.c_long, i32, i32, i32, i32, vp]
+    lib.MPIX_Reduce_local_indexed.restype = i32
+    lib.MPIR_Hip_reduce_indexed.argtypes = [vp, vp, vp, vp, u64, u64, u64, i32, i32, vp, i32]
+    lib.MPIR_Hip_reduce_indexed.restype = i32
+    lib.MPIR_Hip_indexed_plan_info.argtypes = [vp, vp, vp, vp, u64, u64, u64, i32, i32, ctypes.POINTER(u64)]
+    lib.MPIR_Hip_indexed_plan_info.restype = i32
     lib.MPIX_Hip_comm_get_unique_id.argtypes = [vp]
     lib.MPIX_Hip_comm_get_unique_id.restype = i32
     lib.MPIX_Hip_comm_create.argtypes = [vp, i32, i32, ctypes.POINTER(vp)]
@@ -515,6 +522,57 @@ def fetch_plan_info(inbuf: int, inoutbuf: int, fetchbuf: int, count: int, dataty
     if rc:
         raise LookupError(f"MPIR_Hip_fetch_plan_info: {rc}")
     return dict(zip(("path", "groups", "nhead", "ntail"), (int(v) for v in out)))
+
+
+# ---- indexed reductions (MPIX_Reduce_local_indexed)
+INDEXED_EMPTY, INDEXED_SINGLE, INDEXED_WIDE, INDEXED_NARROW_VEC, INDEXED_NARROW_ELEMS = range(5)
+INDEXED_NAMES = ["empty", "single", "wide", "narrow_vec", "narrow_elems"]
+
+
+def _table_addr(table) -> int:
+    """A displacement table's address: None / 0 (no table), a raw address (device
+    memory, or host memory for the synchronous call), or a C-contiguous numpy
+    int64 array (a host table; the caller keeps it alive over the call)."""
+    if table is None or isinstance(table, int):
+        return table or 0
+    if str(table.dtype) != "int64" or not table.flags["C_CONTIGUOUS"]:
+        raise TypeError("a displacement table is a C-contiguous int64 array (MPI_Aint)")
+    return table.ctypes.data
+
+
+def reduce_local_indexed(inbuf: int, in_displs, inoutbuf: int, inout_displs, disp_unit: int, nblocks: int,
+                         blocklen: int, datatype: int, op: int, stream: int = 0) -> int:
+    """MPIX_Reduce_local_indexed: nblocks blocks of blocklen elements, block k at
+    inbuf + in_displs[k] * disp_unit and inoutbuf + inout_displs[k] * disp_unit
+    bytes (raw device addresses; a table None: that side packed), in one launch.
+    A table is a raw address or a numpy int64 array (see _table_addr).  stream 0:
+    synchronous on the library stream (host tables allowed); otherwise enqueued on
+    that HIP stream, no wait (device tables only)."""
+    return load().MPIX_Reduce_local_indexed(ctypes.c_void_p(inbuf or None), ctypes.c_void_p(_table_addr(in_displs) or None),
+                                            ctypes.c_void_p(inoutbuf or None),
+                                            ctypes.c_void_p(_table_addr(inout_displs) or None), disp_unit, nblocks,
+                                            blocklen, datatype, op, ctypes.c_void_p(stream or None))
+
+
+def indexed_plan_info(inbuf: int, in_displs, inoutbuf: int, inout_displs, disp_unit: int, nblocks: int, blocklen: int,
+                      datatype: int, op: int) -> dict:
+    """MPIR_Hip_indexed_plan_info: the launches of an indexed reduction of device
+    operands and tables at these addresses (never dereferenced, the tables only
+    compared with 0; no GPU needed): form (INDEXED_*), launches, groups (over all
+    launches), per (WIDE: G, workgroups per block; NARROW: units per workgroup),
+    threshold (bytes from which a block is wide) and rows_per_launch.  Raises
+    LookupError where the pair has no kernel, ValueError for arguments the call
+    refuses."""
+    out = (ctypes.c_uint64 * 6)()
+    rc = load().MPIR_Hip_indexed_plan_info(ctypes.c_void_p(inbuf or None), ctypes.c_void_p(_table_addr(in_displs) or None),
+                                           ctypes.c_void_p(inoutbuf or None),
+                                           ctypes.c_void_p(_table_addr(inout_displs) or None), disp_unit, nblocks,
+                                           blocklen, op & 0xFF, _ELEM_BY_HANDLE[datatype], out)
+    if rc == MPIR_HIP_EARG:
+        raise ValueError("MPIR_Hip_indexed_plan_info: arguments refused")
+    if rc:
+        raise LookupError(f"MPIR_Hip_indexed_plan_info: {rc}")
+    return dict(zip(("form", "launches", "groups", "per", "threshold", "rows_per_launch"), (int(v) for v in out)))
 
 
 MPIX_HIP_ALG_AUTO = 0
