@@ -56,7 +56,7 @@ enum MPIR_Hip_elem {
 #define MPIR_HIP_ERUNTIME  2   /* HIP runtime failure; see MPIR_Hip_error_string() */
 #define MPIR_HIP_ENOKERNEL 3   /* (op, elem) pair has no kernel */
 #define MPIR_HIP_ENODEV    4   /* no usable GPU */
-#define MPIR_HIP_EARG      5   /* an argument out of range (MPIR_Hip_reduce_strided's strides, MPIR_Hip_reduce_indexed's disp_unit and offsets) */
+#define MPIR_HIP_EARG      5   /* an argument out of range (MPIR_Hip_reduce_strided's strides, MPIR_Hip_reduce_indexed's and MPIR_Hip_reduce_ragged's disp_unit, offsets and tables) */
 
 /* Combine inoutbuf[i] = op(inoutbuf[i], inbuf[i]) for i < count elements of
  * class `elem`.  Pointers may be device, pinned-host or pageable-host memory
@@ -292,6 +292,65 @@ int MPIR_Hip_reduce_indexed(const void *inbuf, const int64_t *in_displs, void *i
 int MPIR_Hip_indexed_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
                                const int64_t *io_displs, uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen,
                                int op, int elem, uint64_t out[6]);
+
+/* Ragged reduction: npieces pieces of unequal length.  starts (npieces + 1
+ * entries) holds the pieces' element offsets in packed order, CSR row pointers:
+ * starts[0] == 0, non-decreasing, starts[npieces] == count; piece k has
+ * starts[k + 1] - starts[k] elements (none is fine) and is
+ * io_k[i] = op(io_k[i], in_k[i]) with in_k = inbuf + in_displs[k] * disp_unit
+ * and io_k = inoutbuf + io_displs[k] * disp_unit bytes (signed displacements);
+ * a side whose table is NULL is packed, piece k at starts[k] * the element's
+ * size.  The pieces of an MPI_Type_indexed / MPI_Type_create_hindexed operand,
+ * or of any IOV, under one (op, elem), in ONE kernel launch always: the grid
+ * goes by packed element (ceil(count * size / 16 KiB) workgroups), not by piece.
+ * Each piece's result is bit-identical to MPIR_Hip_reduce on it; no byte outside
+ * the pieces is read or written, no table is written.  Output pieces that
+ * overlap each other or an input piece are undefined (not checked); a repeated
+ * input piece is fine.
+ * disp_unit == 0, or more than INT64_MAX, is MPIR_HIP_EARG, whatever the
+ * counts.  Otherwise count == 0 succeeds with no pointer looked at, tables
+ * included.  count > 0 with npieces == 0, npieces or count above INT32_MAX, and
+ * starts NULL beside a displacement table are MPIR_HIP_EARG.  Both displacement
+ * tables NULL is MPIR_Hip_reduce on count elements; starts is not looked at.
+ * Residency: both bases must be device memory on one device, and the last byte
+ * of a packed side (else MPIR_HIP_EBUFFER).  Each of the three tables is device
+ * memory on that device, read by the kernel: it must stay unchanged until the
+ * work completes.  A device starts that breaks its three conditions is the
+ * caller's error and what is then combined is undefined; the kernel's table
+ * indices stay inside [0, npieces] all the same.  With sync != 0 and hip_stream
+ * NULL each table may be host memory instead: the library reads it -- starts
+ * for its three conditions (MPIR_HIP_EARG), a displacement table for the
+ * overflow of displs[k] * disp_unit (MPIR_HIP_EARG), both before the operands'
+ * residency is looked at, and, where starts is a host table too so that the
+ * lengths are known, the first byte of the lowest non-empty piece and the last
+ * byte of the highest (MPIR_HIP_EBUFFER) -- and copies it into the per-(thread, device) table buffer, stream-ordered ahead of
+ * the kernel.  A host table in any other call is MPIR_HIP_EBUFFER.  Everything is
+ * checked before anything is enqueued, so a call that fails has written nothing.
+ * With device tables the launch carries everything else in its kernel arguments
+ * (graph-capturable).
+ * A 16-byte chunk of packed space moves as one vector where it lies inside one
+ * piece and both its addresses are multiples of 16, decided per chunk on the
+ * device; other chunks move element by element.
+ * MPIR_HIP_ENOKERNEL for REPLACE and pairs with no kernel. */
+int MPIR_Hip_reduce_ragged(const void *inbuf, const int64_t *in_displs, void *inoutbuf, const int64_t *io_displs,
+                           const int64_t *starts, uint64_t disp_unit, uint64_t npieces, uint64_t count, int op,
+                           int elem, void *hip_stream, int sync);
+
+/* For tests and tools: the launch MPIR_Hip_reduce_ragged would make, from the
+ * same planner the launch runs (host arithmetic on the pointer values and
+ * counts only: the tables are never read, only compared with NULL; no GPU is
+ * needed).  out = {form, launches (1), workgroups, packed elements per
+ * workgroup, rounds of the wave-wide search for a workgroup's first piece
+ * (ceil(log64(npieces + 1))), piece boundaries a workgroup holds in LDS (4
+ * bytes each)}.  SINGLE reports MPIR_Hip_plan_info's grid as its workgroups.
+ * Returns as MPIR_Hip_reduce_ragged does for the same arguments, residency and
+ * the tables' contents apart. */
+#define MPIR_HIP_RAGGED_EMPTY   0   /* count 0: nothing to do */
+#define MPIR_HIP_RAGGED_SINGLE  1   /* both displacement tables NULL: MPIR_Hip_reduce's own plan */
+#define MPIR_HIP_RAGGED_RAGGED  2   /* one launch of k_reduce_ragged */
+int MPIR_Hip_ragged_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
+                              const int64_t *io_displs, const int64_t *starts, uint64_t disp_unit, uint64_t npieces,
+                              uint64_t count, int op, int elem, uint64_t out[6]);
 
 /* Flags for the calling thread's later MPIR_Hip_combine calls; returns the
  * previous flags.  MPIR_HIP_COMBINE_UNCAPPED: the fused folds run without the

@@ -32,6 +32,7 @@ multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+RaggedEntry g_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 
 // Strided rows of at least this many bytes take the wide form (one row's tiles
@@ -733,6 +734,86 @@ int indexed_host_table(const char *base, const int64_t *displs, uint64_t disp_un
     return MPIR_HIP_OK;
 }
 
+// ---- ragged calls: unequal pieces from a table of packed element offsets.
+// the argument checks MPIR_Hip_reduce_ragged makes before it looks at a pointer;
+// MPIR_HIP_OK with *form EMPTY or SINGLE where that settles the call
+int ragged_args(const void *in_displs, const void *io_displs, const void *starts, uint64_t disp_unit, uint64_t npieces,
+                uint64_t count, int op, int elem, int *form) {
+    if (!pair_in_range(op, elem) || !g_ragged[op][elem].launch) return MPIR_HIP_ENOKERNEL;
+    // (before the counts, as the MPIX entry checks it: the two layers answer alike)
+    if (!disp_unit || disp_unit > (~(uint64_t)0 >> 1)) return MPIR_HIP_EARG;
+    *form = MPIR_HIP_RAGGED_EMPTY;
+    if (!count) return MPIR_HIP_OK;
+    // the kernel's piece indices and relative offsets are 32-bit: the public
+    // entry point's ints
+    if (!npieces || npieces > (uint64_t)INT32_MAX || count > (uint64_t)INT32_MAX) return MPIR_HIP_EARG;
+    *form = MPIR_HIP_RAGGED_SINGLE;
+    if (!in_displs && !io_displs) return MPIR_HIP_OK;
+    if (!starts) return MPIR_HIP_EARG;
+    *form = MPIR_HIP_RAGGED_RAGGED;
+    return MPIR_HIP_OK;
+}
+
+// The plan of a RAGGED call: one launch of ragged_groups workgroups, each a span
+// of 16 KiB of packed elements; the rounds of the wave-wide search and the
+// boundaries a workgroup holds in LDS come from the kernel's own constants.
+// Host arithmetic on the counts alone: no table is read.
+struct RaggedPlan {
+    uint64_t groups, per, rounds, lds_entries;
+};
+void ragged_plan(uint64_t npieces, uint64_t count, int elem, RaggedPlan &p) {
+    const uint64_t esz = g_elem_size[elem];
+    p.groups = ragged_groups(count, esz);
+    p.per = kTileBytes / esz;
+    p.rounds = ragged_search_rounds(npieces);
+    p.lds_entries = kRaggedLdsEntries;
+}
+
+// A host `starts`, read before anything is enqueued: starts[0] == 0, no entry
+// below the one before it, starts[npieces] == count (else MPIR_HIP_EARG)
+int ragged_host_starts(const int64_t *starts, uint64_t npieces, uint64_t count) {
+    if (starts[0] != 0 || starts[npieces] != (int64_t)count) return MPIR_HIP_EARG;
+    for (uint64_t k = 0; k < npieces; ++k)
+        if (starts[k + 1] < starts[k]) return MPIR_HIP_EARG;
+    return MPIR_HIP_OK;
+}
+
+// A host displacement table: every displs[k] * disp_unit must fit 64 signed
+// bits (MPIR_HIP_EARG)
+int ragged_host_products(const int64_t *displs, uint64_t disp_unit, uint64_t npieces) {
+    for (uint64_t k = 0; k < npieces; ++k) {
+        int64_t off;
+        if (__builtin_mul_overflow(displs[k], (int64_t)disp_unit, &off)) return MPIR_HIP_EARG;
+    }
+    return MPIR_HIP_OK;
+}
+
+// ... and beside a host `starts` (both already checked) the pieces' lengths are
+// known too: the first byte of the lowest non-empty piece and the last byte of
+// the highest must be device memory on `dev` (MPIR_HIP_EBUFFER; an end past 64
+// signed bits MPIR_HIP_EARG).  Beside a device `starts` the lengths are the
+// kernel's to read, and only the products are checked.
+int ragged_host_extremes(const char *base, const int64_t *displs, const int64_t *host_starts, uint64_t disp_unit,
+                         uint64_t npieces, uint64_t esz, int dev) {
+    int64_t lo = INT64_MAX, hi = INT64_MIN;     // first byte of the lowest, last byte of the highest
+    for (uint64_t k = 0; k < npieces; ++k) {
+        if (host_starts[k + 1] == host_starts[k]) continue;
+        const int64_t off = displs[k] * (int64_t)disp_unit;
+        int64_t last;
+        if (__builtin_add_overflow(off, (int64_t)((uint64_t)(host_starts[k + 1] - host_starts[k]) * esz - 1), &last))
+            return MPIR_HIP_EARG;
+        lo = std::min(lo, off);
+        hi = std::max(hi, last);
+    }
+    const void *ends[2] = {base + lo, base + hi};   // (count > 0: some piece is not empty)
+    DeviceSpan span;
+    for (int k = 0; k < 2; ++k) {
+        int d = -1;
+        if (classify_in_span(ends[k], &d, span) != LOC_DEVICE || d != dev) return MPIR_HIP_EBUFFER;
+    }
+    return MPIR_HIP_OK;
+}
+
 // the argument checks MPIR_Hip_reduce_fetch makes before it looks at a pointer;
 // MPIR_HIP_OK with *path EMPTY or COPY where that settles the call, else TILE
 // (the plan then says which of the kernel's two paths)
@@ -1297,6 +1378,126 @@ int MPIR_Hip_reduce_indexed(const void *inbuf, const int64_t *in_displs, void *i
     // (launches made before one that failed are still queued on the library stream)
     if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
     if (e != hipSuccess) rc = set_err(e, "indexed launch");
+    else if (sync) rc = wait_stream(dev, s);
+    return rc;
+}
+
+int MPIR_Hip_ragged_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
+                              const int64_t *io_displs, const int64_t *starts, uint64_t disp_unit, uint64_t npieces,
+                              uint64_t count, int op, int elem, uint64_t out[6]) {
+    int form = 0;
+    const int rc = ragged_args(in_displs, io_displs, starts, disp_unit, npieces, count, op, elem, &form);
+    if (rc != MPIR_HIP_OK) return rc;
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    out[0] = (uint64_t)form;
+    if (form == MPIR_HIP_RAGGED_EMPTY) return MPIR_HIP_OK;
+    if (form == MPIR_HIP_RAGGED_SINGLE) {
+        // the single call's own plan (MPIR_Hip_plan_info)
+        const plan_fn fn = g_table[op][elem].plan ? g_table[op][elem].plan : g_table[op][elem].wide;
+        if (!fn) return MPIR_HIP_ENOKERNEL;
+        ReducePlan p;
+        fn(inbuf, const_cast<void *>(inoutbuf), count, &p);
+        out[1] = 1;
+        out[2] = p.groups;
+        return MPIR_HIP_OK;
+    }
+    RaggedPlan p;
+    ragged_plan(npieces, count, elem, p);
+    out[1] = 1;
+    out[2] = p.groups;
+    out[3] = p.per;
+    out[4] = p.rounds;
+    out[5] = p.lds_entries;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_reduce_ragged(const void *inbuf, const int64_t *in_displs, void *inoutbuf, const int64_t *io_displs,
+                           const int64_t *starts, uint64_t disp_unit, uint64_t npieces, uint64_t count, int op,
+                           int elem, void *hip_stream, int sync) {
+    int form = 0;
+    int rc = ragged_args(in_displs, io_displs, starts, disp_unit, npieces, count, op, elem, &form);
+    if (rc != MPIR_HIP_OK || form == MPIR_HIP_RAGGED_EMPTY) return rc;
+    ctx().err[0] = 0;
+    // Everything is settled before anything is enqueued (a call that fails has
+    // written nothing).  First the tables: each is device memory, both its ends,
+    // or, in a synchronous call on the library stream, host memory, which is
+    // then read for what is wrong with it whatever the operands are -- starts
+    // for its three conditions, a displacement table for its products
+    // (MPIR_HIP_EARG).  Then residency: both bases on one device; the last byte
+    // of a packed side; the device tables on that device; and, where starts is a
+    // host table beside a host displacement table, the pieces' extremes.
+    const uint64_t esz = g_elem_size[elem];
+    const char *base[2] = {static_cast<const char *>(inbuf), static_cast<char *>(inoutbuf)};
+    // both tables NULL: the single call, and starts is not looked at
+    const bool single = form == MPIR_HIP_RAGGED_SINGLE;
+    const int64_t *table[3] = {in_displs, io_displs, single ? nullptr : starts};
+    const uint64_t entries[3] = {npieces, npieces, npieces + 1};
+    bool host_table[3] = {false, false, false};
+    int table_dev[3] = {-1, -1, -1};
+    for (int k = 2; k >= 0; --k) {
+        if (!table[k]) continue;
+        DeviceSpan ts;
+        if (classify_in_span(table[k], &table_dev[k], ts) == LOC_DEVICE) {
+            int d2 = -1;
+            if (classify_in_span(reinterpret_cast<const char *>(table[k] + entries[k]) - 1, &d2, ts) != LOC_DEVICE ||
+                d2 != table_dev[k])
+                return MPIR_HIP_EBUFFER;
+            continue;
+        }
+        if (hip_stream || !sync) return MPIR_HIP_EBUFFER;       // a host table would be read after the call returned
+        host_table[k] = true;
+        rc = k == 2 ? ragged_host_starts(starts, npieces, count) : ragged_host_products(table[k], disp_unit, npieces);
+        if (rc != MPIR_HIP_OK) return rc;
+    }
+    int dev = -1;
+    DeviceSpan span[2];
+    for (int k = 0; k < 2; ++k) {
+        int d = -1;
+        if (classify_in_span(base[k], &d, span[k]) != LOC_DEVICE || (k && d != dev)) return MPIR_HIP_EBUFFER;
+        dev = d;
+        if (!table[k] && (classify_in_span(base[k] + (count * esz - 1), &d, span[k]) != LOC_DEVICE || d != dev))
+            return MPIR_HIP_EBUFFER;
+    }
+    if (single) return MPIR_Hip_reduce(inbuf, inoutbuf, count, op, elem, hip_stream, sync);
+    for (int k = 0; k < 3; ++k) {
+        if (!table[k]) continue;
+        if (!host_table[k] && table_dev[k] != dev) return MPIR_HIP_EBUFFER;
+        if (host_table[k] && k < 2 && host_table[2]) {
+            rc = ragged_host_extremes(base[k], table[k], starts, disp_unit, npieces, esz, dev);
+            if (rc != MPIR_HIP_OK) return rc;
+        }
+    }
+    DeviceScope on(dev);
+    if (!on.ok()) return on.err();
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!s) rc = get_stream(dev, S_MAIN, &s);
+    if (rc != MPIR_HIP_OK) return rc;
+    if (host_table[0] || host_table[1] || host_table[2]) {
+        // host tables into the thread's table buffer, stream-ordered ahead of the
+        // kernel (the earlier synchronous call that read the buffer has returned)
+        size_t total = 0;
+        for (int k = 0; k < 3; ++k) total += host_table[k] ? (size_t)entries[k] * sizeof(int64_t) : 0;
+        char *buf = nullptr;
+        rc = get_tables(dev, total, &buf);
+        if (rc != MPIR_HIP_OK) return rc;               // (nothing of this call is queued yet)
+        for (int k = 0; k < 3; ++k) {
+            if (!host_table[k]) continue;
+            const size_t tbytes = (size_t)entries[k] * sizeof(int64_t);
+            const hipError_t ce = hipMemcpyAsync(buf, table[k], tbytes, hipMemcpyHostToDevice, s);
+            if (ce != hipSuccess) {
+                // (another table's copy may be queued on the library stream)
+                ctx().dev[dev].main_pending = true;
+                return set_err(ce, "ragged table copy");
+            }
+            table[k] = reinterpret_cast<const int64_t *>(buf);
+            buf += tbytes;
+        }
+    }
+    const RaggedArgs a{base[0], static_cast<char *>(inoutbuf), table[0], table[1], table[2], disp_unit,
+                       (uint32_t)npieces, (uint32_t)count};
+    const hipError_t e = g_ragged[op][elem].launch(&a, s);
+    if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
+    if (e != hipSuccess) rc = set_err(e, "ragged launch");
     else if (sync) rc = wait_stream(dev, s);
     return rc;
 }

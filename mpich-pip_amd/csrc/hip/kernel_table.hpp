@@ -36,6 +36,7 @@ typedef uint64_t (*bgroups_fn)(const void *, const void *, uint64_t, int *);
 typedef hipError_t (*strided_fn)(const StridedArgs *, uint64_t, hipStream_t);
 typedef hipError_t (*fetch_fn)(const FetchArgs *, hipStream_t);
 typedef hipError_t (*indexed_fn)(const IndexedArgs *, uint64_t, hipStream_t);
+typedef hipError_t (*ragged_fn)(const RaggedArgs *, hipStream_t);
 typedef void (*fplan_fn)(const FetchArgs *, FetchPlan *);
 
 // plan: plan_reduce<T> (reduce_kernels.hpp) for the classes whose launcher is
@@ -67,6 +68,10 @@ struct FetchEntry { fetch_fn launch; fplan_fn plan; };
 // k_reduce_indexed over a range of blocks (MPIR_Hip_reduce_indexed), for the
 // pairs g_batch holds (reg_indexed<>, from the reg_indexed_*.hip units).
 struct IndexedEntry { indexed_fn launch; };
+// g_ragged[op][elem], likewise: launch_ragged<Op, T>, the one launch of
+// k_reduce_ragged (MPIR_Hip_reduce_ragged), for the pairs g_indexed holds
+// (reg_ragged<>, from the reg_ragged_*.hip units).
+struct RaggedEntry { ragged_fn launch; };
 
 // float / double SUM and PROD on the host: the SSE instruction itself.  The
 // reference's loop `a[i] = a[i] + b[i]` (opsum.c:21-76, gcc -O2) is an
@@ -138,6 +143,7 @@ extern BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern RaggedEntry g_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 constexpr int kMultiMaxP = 8;
 extern multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 
@@ -176,6 +182,11 @@ void reg_fetch(int op, int elem) {
 template <class Op, class T>
 void reg_indexed(int op, int elem) {
     g_indexed[op][elem] = IndexedEntry{&launch_indexed<Op, T>};
+}
+// the ragged kernel of the same pairs, from the reg_ragged_*.hip units
+template <class Op, class T>
+void reg_ragged(int op, int elem) {
+    g_ragged[op][elem] = RaggedEntry{&launch_ragged<Op, T>};
 }
 template <class Op, class T>
 void reg_multi(int op, int elem) {

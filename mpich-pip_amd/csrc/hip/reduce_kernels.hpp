@@ -1091,6 +1091,314 @@ hipError_t launch_indexed(const IndexedArgs *a, uint64_t groups, hipStream_t s) 
 }
 
 // ============================================================================
+// Ragged reductions (MPIR_Hip_reduce_ragged): npieces unequal pieces, piece k of
+// starts[k + 1] - starts[k] elements (starts: npieces + 1 packed element offsets,
+// CSR row pointers, a device table) at in + in_displs[k] * disp_unit and io +
+// io_displs[k] * disp_unit; a side with no table is packed (piece k at
+// starts[k] elements).  The target of an accumulate on an MPI_Type_indexed /
+// hindexed type, or any IOV the segment code makes (do_accumulate_op,
+// mpidrma.h:930-1021: starts is its running accumulated_count).
+//
+// Work goes by packed element, never by piece (a 3-element and a 3-million-
+// element piece may share a call): workgroup g owns packed elements [g, g + 1) x
+// kTileBytes / sizeof(T), the element paths' span everywhere else here, so the
+// grid is ceil(count x sizeof(T) / 16 KiB), known on the host without a table,
+// and the call is one launch always.
+//
+//   * The span's first piece, the largest p with starts[p] <= the span's first
+//     element (so empty pieces before it are skipped), comes from a wave-wide
+//     64-ary search: each lane probes one of 64 evenly spaced entries of the
+//     range, a ballot and a population count pick the sub-range;
+//     ceil(log64(npieces + 1)) dependent rounds (ragged_search_rounds) where a
+//     binary search had ceil(log2).  Each wave searches for itself (no LDS, no
+//     barrier); the result passes through readfirstlane.  The range is narrowed
+//     by index arithmetic alone, so whatever the table holds no index leaves
+//     [0, npieces].
+//   * The piece boundaries inside the span go to LDS, 32-bit and relative to
+//     the span's first element, 256 entries a pass until one reaches the span's
+//     end (entries past starts[npieces] count as the end), at most
+//     kRaggedLdsEntries.  With the first pass go the loads of the two
+//     displacement tables' entries for the span's first 256 pieces, whose
+//     products with disp_unit are kept in LDS as well.  A lane finds the piece
+//     of each of its units by a binary search there.  A unit beyond the last boundary held (a span with
+//     more boundaries than the table: one-byte elements in one-element pieces)
+//     searches the global table from there on, again bounded by index.
+//   * A lane's unit is a 16-byte chunk of PACKED space (V = 16 / sizeof(T)
+//     elements; one element for the 32-byte classes).  The host cannot read a
+//     device table, so the form is chosen per chunk on the device: a chunk that
+//     lies inside one piece, does not pass count, and whose two byte addresses
+//     are multiples of 16 moves as one nt global_load_dwordx4 per operand,
+//     combine16, one nt global_store_dwordx4; any other chunk goes element by
+//     element through batch_elem_at, each element stepping forward to its own
+//     piece.  A lane looks up its units' pieces, then reads all their
+//     byte offsets in one run (from LDS, or from the tables for a piece past
+//     the span's 256th), then issues its vector loads together.
+//
+// 256 threads, 56 bytes of kernel arguments, 15 KiB of static LDS (eight
+// workgroups' worth fits a CU), no scratch, no gridDim.
+// ============================================================================
+struct RaggedArgs {
+    const char *in;             // the bases
+    char *io;
+    const int64_t *in_displs;   // npieces entries; null: packed
+    const int64_t *io_displs;
+    const int64_t *starts;      // npieces + 1 entries
+    uint64_t disp_unit;         // bytes per displacement unit, > 0
+    uint32_t npieces;           // > 0
+    uint32_t count;             // packed elements, > 0
+};
+
+// count is an int at the public entry point: (2^31 - 1) elements of at most 32
+// bytes are fewer than 2^22 spans of 16 KiB -- one launch always
+static_assert(((uint64_t)INT32_MAX * 32 + kTileBytes - 1) / kTileBytes < kBatchMaxGroups,
+              "a ragged reduction of INT_MAX elements must fit one launch");
+
+// boundaries a workgroup keeps in LDS: 11 passes of 256, 11 KiB; and the byte
+// offsets of the span's first 256 pieces on both sides, 4 KiB
+constexpr uint32_t kRaggedLdsEntries = 11 * kThreads;
+constexpr uint32_t kRaggedLdsOffsets = kThreads;
+static_assert(kRaggedLdsEntries * sizeof(uint32_t) + 2 * kRaggedLdsOffsets * sizeof(uint64_t) <= (16u << 10),
+              "static LDS of at most 16 KiB");
+
+// the workgroups of a call, and the search's rounds: the least r with 64^r >= npieces + 1
+inline uint64_t ragged_groups(uint64_t count, size_t esz) { return (count * esz + kTileBytes - 1) / kTileBytes; }
+inline uint32_t ragged_search_rounds(uint64_t npieces) {
+    uint32_t r = 0;
+    for (uint64_t m = npieces + 1; m > 1; m = (m + 63) >> 6) ++r;
+    return r;
+}
+
+// The largest p in [0, npieces] with starts[p] <= e0 (starts[0] == 0 makes one
+// exist).  [lo, hi) holds it; a round probes lo + lane * step, step = ceil((hi -
+// lo) / 64): the lanes whose entry is <= e0 are a prefix, c of them, and the
+// answer lies in [lo + (c - 1) * step, lo + c * step).  Only lanes with a probe
+// below hi count, so the new range is inside the old one whatever was loaded.
+__device__ __forceinline__ uint32_t ragged_first_piece(const int64_t *starts, uint32_t npieces, uint64_t e0) {
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t lo = 0, hi = npieces + 1;
+    while (hi - lo > 1) {
+        const uint32_t step = (hi - lo + 63) >> 6;
+        const uint64_t q = (uint64_t)lo + (uint64_t)lane * step;
+        const bool le = q < hi && starts[q] <= (int64_t)e0;
+        uint32_t c = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(le));
+        c = c ? c : 1;
+        lo += (c - 1) * step;
+        hi = lo + step < hi ? lo + step : hi;
+    }
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+}
+
+// what a workgroup knows of its span
+struct RaggedSpan {
+    const int64_t *starts;
+    const uint32_t *bnd;    // LDS: min(starts[p0 + 1 + i] - e0, len), i < nvalid
+    const uint64_t *off_in, *off_io;    // LDS: displs[p0 + i] * disp_unit, i < kRaggedLdsOffsets (sides with a table)
+    uint32_t e0;            // the span's first packed element
+    int32_t s0;             // starts[p0] - e0, <= 0
+    uint32_t len;           // elements in the span (count clips the last)
+    uint32_t p0;            // the span's first piece
+    uint32_t nvalid;        // boundaries in LDS
+    uint32_t npieces;
+};
+// a piece as a lane holds it: its index and its elements [s, e) relative to the
+// span's first (e clipped to the span's length)
+struct RaggedPiece {
+    uint32_t k;
+    int32_t s, e;
+};
+
+// starts[m] relative to the span, clipped to [0, len]; past the table: len
+__device__ __forceinline__ int32_t ragged_bound(const RaggedSpan &w, uint64_t m) {
+    const uint64_t i = m - w.p0 - 1;
+    if (i < w.nvalid) return (int32_t)w.bnd[i];
+    if (m > w.npieces) return (int32_t)w.len;
+    const int64_t v = w.starts[m] - (int64_t)w.e0;
+    return (int32_t)(v < 0 ? 0 : v < (int64_t)w.len ? v : (int64_t)w.len);
+}
+
+// The piece that holds element r of the span (r < len), from the boundaries in
+// LDS; false where r lies beyond the last of them (p is then piece p0, a valid
+// index to load by, and not r's piece).
+__device__ __forceinline__ bool ragged_piece_lds(const RaggedSpan &w, uint32_t r, RaggedPiece &p) {
+    uint32_t lo = 0, hi = w.nvalid;         // the boundaries <= r are bnd[0, lo)
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (w.bnd[mid] <= r) lo = mid + 1;
+        else hi = mid;
+    }
+    const bool found = lo < w.nvalid;
+    const uint32_t j = found ? lo : 0;
+    p.k = w.p0 + j;
+    p.s = j ? (int32_t)w.bnd[j - 1] : w.s0;
+    p.e = (int32_t)w.bnd[j];
+    return found;
+}
+
+// ... and from the global table where LDS does not reach: the largest k in
+// [p0 + nvalid, npieces] with starts[k] <= e0 + r, the range halved by index
+__device__ __forceinline__ void ragged_piece_far(const RaggedSpan &w, uint32_t r, RaggedPiece &p) {
+    uint64_t a = (uint64_t)w.p0 + w.nvalid, b = (uint64_t)w.npieces + 1;
+    if (a > w.npieces) a = w.npieces;
+    while (b - a > 1) {
+        const uint64_t mid = (a + b) >> 1;
+        if (w.starts[mid] <= (int64_t)((uint64_t)w.e0 + r)) a = mid;
+        else b = mid;
+    }
+    p.k = (uint32_t)a;
+    p.s = (int32_t)(w.starts[a] - (int64_t)w.e0);
+    p.e = ragged_bound(w, a + 1);
+}
+
+// piece k's byte offset on one side: its table entry times disp_unit (wrapping
+// as pointer arithmetic does), from LDS for the span's first pieces, or its
+// packed place.  k is kept below npieces, the tables' length, whatever starts
+// held.
+__device__ __forceinline__ uint64_t ragged_off(const RaggedSpan &w, const int64_t *displs, const uint64_t *held,
+                                               uint64_t disp_unit, const RaggedPiece &p, size_t esz) {
+    if (!displs) return (uint64_t)((int64_t)w.e0 + p.s) * esz;
+    const uint32_t k = p.k < w.npieces ? p.k : w.npieces - 1;
+    const uint32_t j = k - w.p0;
+    return j < kRaggedLdsOffsets ? held[j] : (uint64_t)displs[k] * disp_unit;
+}
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_reduce_ragged(RaggedArgs a) {
+    constexpr uint32_t per = kTileBytes / sizeof(T);                    // the span's elements
+    constexpr uint32_t V = sizeof(T) <= 16 ? 16 / sizeof(T) : 1;        // a unit's elements
+    constexpr int per_lane = (int)(per / V / kThreads);
+    __shared__ uint32_t bnd[kRaggedLdsEntries];
+    __shared__ uint64_t off_in[kRaggedLdsOffsets], off_io[kRaggedLdsOffsets];
+    const unsigned t = threadIdx.x;
+    const uint64_t e0 = (uint64_t)blockIdx.x * per;
+    if (e0 >= a.count) return;
+    RaggedSpan w;
+    w.starts = a.starts;
+    w.bnd = bnd;
+    w.off_in = off_in;
+    w.off_io = off_io;
+    w.npieces = a.npieces;
+    w.e0 = (uint32_t)e0;
+    w.len = a.count - w.e0 < per ? a.count - w.e0 : per;
+    w.p0 = ragged_first_piece(a.starts, a.npieces, e0);
+    w.s0 = (int32_t)(a.starts[w.p0] - (int64_t)e0);
+    // The first 256 boundaries after starts[p0], and with them the byte offsets
+    // of pieces p0 ... p0 + 255 on the sides with a table: three loads at
+    // indices kept inside the tables (a side with no table reads starts, and the
+    // value is never used), none behind a branch, so that they leave together
+    // and a lane that has found its unit's piece in LDS finds the piece's place
+    // there too, not one more trip to memory away.
+    {
+        const uint64_t k = (uint64_t)w.p0 + t < a.npieces ? (uint64_t)w.p0 + t : a.npieces - 1;
+        const uint64_t m = (uint64_t)w.p0 + 1 + t;
+        const int64_t di = (a.in_displs ? a.in_displs : a.starts)[k];
+        const int64_t dj = (a.io_displs ? a.io_displs : a.starts)[k];
+        int64_t v = a.starts[m <= a.npieces ? m : a.npieces] - (int64_t)e0;
+        v = m > a.npieces || v > (int64_t)w.len ? (int64_t)w.len : v < 0 ? 0 : v;
+        off_in[t] = (uint64_t)di * a.disp_unit;
+        off_io[t] = (uint64_t)dj * a.disp_unit;
+        bnd[t] = (uint32_t)v;
+    }
+    w.nvalid = kThreads;
+    __syncthreads();
+    // further passes of 256 until a pass's last boundary has reached the span's
+    // end (they do not decrease; past the table every entry is the end)
+    while (bnd[w.nvalid - 1] < w.len && w.nvalid < kRaggedLdsEntries) {
+        const uint64_t m = (uint64_t)w.p0 + 1 + w.nvalid + t;
+        int64_t v = a.starts[m <= a.npieces ? m : a.npieces] - (int64_t)e0;
+        v = m > a.npieces || v > (int64_t)w.len ? (int64_t)w.len : v < 0 ? 0 : v;
+        bnd[w.nvalid + t] = (uint32_t)v;
+        w.nvalid += kThreads;
+        __syncthreads();
+    }
+
+    // bit j: the lane's unit j is still to do
+    uint32_t todo = 0;
+#pragma unroll
+    for (int j = 0; j < per_lane; ++j) todo |= (uint32_t)((t + (uint32_t)j * kThreads) * V < w.len) << j;
+
+    if constexpr (sizeof(T) <= 16) {
+        // the chunks that can go as vectors: each unit's piece from LDS, then
+        // both sides' displacement loads in one run (a packed side loads nothing),
+        // then the data loads of the chunks that qualify
+        RaggedPiece p[per_lane];
+        uintptr_t pi[per_lane], po[per_lane];
+        u32x4 x[per_lane], y[per_lane];
+        bool vec[per_lane];
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) {
+            const uint32_t r = (t + (uint32_t)j * kThreads) * V;
+            // inside one piece (whose end is clipped to the span's, and so to count)
+            vec[j] = ragged_piece_lds(w, r < w.len ? r : w.len - 1, p[j]) && (todo >> j & 1) &&
+                     (int32_t)(r + V) <= p[j].e;
+        }
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) po[j] = ragged_off(w, a.io_displs, off_io, a.disp_unit, p[j], sizeof(T));
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) pi[j] = ragged_off(w, a.in_displs, off_in, a.disp_unit, p[j], sizeof(T));
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) {
+            const uint32_t r = (t + (uint32_t)j * kThreads) * V;
+            const uint64_t d = (uint64_t)(int64_t)((int32_t)r - p[j].s) * sizeof(T);    // bytes into the piece
+            pi[j] += reinterpret_cast<uintptr_t>(a.in) + d;
+            po[j] += reinterpret_cast<uintptr_t>(a.io) + d;
+            vec[j] = vec[j] && ((pi[j] | po[j]) & 15) == 0;
+        }
+        // No branch around the loads, so that all of a lane's leave together and
+        // it waits once: a chunk that goes by elements loads the first 16 bytes
+        // of starts instead (two entries, which every table has) and drops them.
+        // Only the stores are guarded.
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) {
+            const uintptr_t spare = reinterpret_cast<uintptr_t>(a.starts);
+            x[j] = __builtin_nontemporal_load(reinterpret_cast<const global_u32x4 *>(vec[j] ? po[j] : spare));
+            y[j] = __builtin_nontemporal_load(reinterpret_cast<const global_u32x4 *>(vec[j] ? pi[j] : spare));
+        }
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) {
+            if (vec[j]) {
+                __builtin_nontemporal_store(combine16<Op, T>(x[j], y[j]), reinterpret_cast<global_u32x4 *>(po[j]));
+                todo &= ~(1u << j);
+            }
+        }
+    }
+    // the other units, element by element: an element at or past its piece's end
+    // steps to the next piece that holds one (empty pieces fall through)
+#pragma unroll 1
+    for (uint32_t j = 0; j < (uint32_t)per_lane; ++j) {
+        if (!(todo >> j & 1)) continue;
+        const uint32_t r = (t + j * kThreads) * V;
+        RaggedPiece q;
+        if (!ragged_piece_lds(w, r, q)) ragged_piece_far(w, r, q);
+        uint64_t qi = ragged_off(w, a.in_displs, off_in, a.disp_unit, q, sizeof(T));
+        uint64_t qo = ragged_off(w, a.io_displs, off_io, a.disp_unit, q, sizeof(T));
+        for (uint32_t i = 0; i < V && r + i < w.len; ++i) {
+            const int32_t e = (int32_t)(r + i);
+            if (e >= q.e) {
+                // (past the table every bound is the span's length, above e: the walk ends)
+                do {
+                    ++q.k;
+                    q.s = q.e;
+                    q.e = ragged_bound(w, (uint64_t)q.k + 1);
+                } while (e >= q.e);
+                qi = ragged_off(w, a.in_displs, off_in, a.disp_unit, q, sizeof(T));
+                qo = ragged_off(w, a.io_displs, off_io, a.disp_unit, q, sizeof(T));
+            }
+            batch_elem_at<Op, T>(a.in + qi, a.io + qo, (uint64_t)(int64_t)(e - q.s));
+        }
+    }
+}
+
+// one launch, always: the grid is the packed elements' spans
+template <class Op, class T>
+hipError_t launch_ragged(const RaggedArgs *a, hipStream_t s) {
+    const uint64_t groups = ragged_groups(a->count, sizeof(T));
+    if (!a->npieces || !a->count || !a->disp_unit || !a->starts || groups < 1 || groups > kBatchMaxGroups)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_reduce_ragged<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+// ============================================================================
 // Fetching reductions (MPIR_Hip_reduce_fetch): fetch[i] = the bytes io[i] held,
 // io[i] = op(io[i], in[i]), in ONE pass -- the target side of MPI_Get_accumulate
 // and MPI_Fetch_and_op, which copies the target's old contents into the response

@@ -47,7 +47,7 @@ struct DevCtx {
     size_t bounce_bytes = 0;
     char *zc = nullptr;          // pinned, device-mapped slot for small mixed-residency calls
     size_t zc_bytes = 0;
-    char *tables = nullptr;      // device copy of a synchronous indexed call's host displacement tables
+    char *tables = nullptr;      // device copy of a synchronous indexed / ragged call's host tables
     size_t tables_bytes = 0;
 };
 
@@ -210,8 +210,9 @@ inline int get_zc(int dev, size_t bytes, char **out) {
     return MPIR_HIP_OK;
 }
 
-// the calling thread's displacement-table buffer on `dev` (MPIR_Hip_reduce_indexed's
-// host tables).  Not `scratch`: stream-variant work may still be reading that,
+// the calling thread's table buffer on `dev`: one call's host tables side by
+// side in `bytes` (MPIR_Hip_reduce_indexed's two displacement tables,
+// MPIR_Hip_reduce_ragged's two and its starts).  Not `scratch`: stream-variant work may still be reading that,
 // while this buffer's only readers are synchronous calls, complete when they
 // returned -- but for one that failed after it enqueued, hence the wait.
 inline int get_tables(int dev, size_t bytes, char **out) {

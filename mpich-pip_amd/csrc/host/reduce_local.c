@@ -749,6 +749,90 @@ static int reduce_local_indexed(const void *inbuf, const MPI_Aint * in_displs, v
     return MPI_SUCCESS;
 }
 
+/* ---- MPIX_Reduce_local_ragged: unequal pieces from a table of packed offsets (see the header) */
+/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
+#pragma weak MPIR_Hip_reduce_ragged
+static int reduce_local_ragged(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                               const MPI_Aint * inout_displs, const MPI_Aint * starts, MPI_Aint disp_unit,
+                               int npieces, int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream);
+
+int MPIX_Reduce_local_ragged(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                             const MPI_Aint * inout_displs, const MPI_Aint * starts, MPI_Aint disp_unit,
+                             int npieces, int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    int rc;
+    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
+    rc = reduce_local_ragged(inbuf, in_displs, inoutbuf, inout_displs, starts, disp_unit, npieces, count, datatype,
+                             op, hip_stream);
+    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
+    return rc;
+}
+
+static int reduce_local_ragged(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                               const MPI_Aint * inout_displs, const MPI_Aint * starts, MPI_Aint disp_unit,
+                               int npieces, int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    static const char *fc = "MPIX_Reduce_local_ragged";
+    int mpi_errno, opidx, elem, rc;
+    _Static_assert(sizeof(MPI_Aint) == sizeof(int64_t), "the shim's tables are 64-bit entries");
+    /* the indexed call's checks in the indexed call's order, npieces and count
+     * where it has nblocks and blocklen */
+    if (npieces < 0 || count < 0) {
+        MPIR_Err_set_detail("negative %s %d", npieces < 0 ? "npieces" : "count", npieces < 0 ? npieces : count);
+        return err_return(fc, MPI_ERR_COUNT);
+    }
+    /* an empty call's pointers are not looked at (the op still is) */
+    mpi_errno = count == 0 ? validate(NULL, NULL, 0, datatype, op) : validate(inbuf, inoutbuf, count, datatype, op);
+    if (mpi_errno != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
+    if (disp_unit <= 0) {
+        MPIR_Err_set_detail("disp_unit %ld is not positive", (long) disp_unit);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (count == 0)
+        return MPI_SUCCESS;
+    if (npieces == 0) {
+        MPIR_Err_set_detail("count %d with no pieces", count);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (starts == NULL && (in_displs != NULL || inout_displs != NULL)) {
+        MPIR_Err_set_detail("a displacement table needs starts");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
+        MPIR_Err_set_detail("user MPI_Op functions run on the host; use MPI_Reduce_local");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    opidx = op & 0xf;
+    elem = MPIR_Op_resolve_elem(opidx, datatype);
+    if (!elem) {        /* compute switch `default:` (LAND/LOR on floats) */
+        MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    if (!MPIR_Hip_reduce_ragged) {
+        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_ragged");
+        return err_return(fc, MPI_ERR_OTHER);
+    }
+    rc = MPIR_Hip_reduce_ragged(inbuf, (const int64_t *) in_displs, inoutbuf, (const int64_t *) inout_displs,
+                                (const int64_t *) starts, (uint64_t) disp_unit, (uint64_t) npieces, (uint64_t) count,
+                                opidx, elem, hip_stream, hip_stream == NULL);
+    if (rc == MPIR_HIP_EBUFFER) {
+        MPIR_Err_set_detail("%s needs device-resident operands on one device, and its tables there too "
+                            "(host tables: the synchronous call only)", fc);
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (rc == MPIR_HIP_EARG) {
+        MPIR_Err_set_detail("%s: starts is not 0, non-decreasing and ending at count, or a piece's offset does not "
+                            "fit the address space", fc);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (rc != MPIR_HIP_OK) {
+        MPIR_Op_report_hip_error(fc, rc);
+        return err_return(fc, *MPIR_Op_errno_ptr());
+    }
+    return MPI_SUCCESS;
+}
+
 /* ---- MPI_Op_create / MPI_Op_free / MPI_Op_commutative ------------------ */
 int PMPI_Op_create(MPI_User_function * user_fn, int commute, MPI_Op * op)
 {

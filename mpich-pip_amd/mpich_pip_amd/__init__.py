@@ -116,6 +116,7 @@ EXPORTED_SYMBOLS = [
     "MPIR_Hip_set_strided_wide_bytes", "MPIR_Hip_strided_test_max_groups",
     "MPIX_Reduce_local_fetch", "MPIR_Hip_reduce_fetch", "MPIR_Hip_fetch_plan_info",
     "MPIX_Reduce_local_indexed", "MPIR_Hip_reduce_indexed", "MPIR_Hip_indexed_plan_info",
+    "MPIX_Reduce_local_ragged", "MPIR_Hip_reduce_ragged", "MPIR_Hip_ragged_plan_info",
     # device collectives (include/mpix_hip_coll.h)
     "MPIX_Hip_comm_get_unique_id", "MPIX_Hip_comm_create", "MPIX_Hip_comm_create_loopback",
     "MPIX_Hip_comm_free", "MPIX_Hip_comm_rank", "MPIX_Hip_comm_size",
@@ -207,6 +208,12 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.MPIR_Hip_reduce_indexed.restype = i32
     lib.MPIR_Hip_indexed_plan_info.argtypes = [vp, vp, vp, vp, u64, u64, u64, i32, i32, ctypes.POINTER(u64)]
     lib.MPIR_Hip_indexed_plan_info.restype = i32
+    lib.MPIX_Reduce_local_ragged.argtypes = [vp, vp, vp, vp, vp, ctypes.c_long, i32, i32, i32, i32, vp]
+    lib.MPIX_Reduce_local_ragged.restype = i32
+    lib.MPIR_Hip_reduce_ragged.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, vp, i32]
+    lib.MPIR_Hip_reduce_ragged.restype = i32
+    lib.MPIR_Hip_ragged_plan_info.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, ctypes.POINTER(u64)]
+    lib.MPIR_Hip_ragged_plan_info.restype = i32
     lib.MPIX_Hip_comm_get_unique_id.argtypes = [vp]
     lib.MPIX_Hip_comm_get_unique_id.restype = i32
     lib.MPIX_Hip_comm_create.argtypes = [vp, i32, i32, ctypes.POINTER(vp)]
@@ -573,6 +580,50 @@ def indexed_plan_info(inbuf: int, in_displs, inoutbuf: int, inout_displs, disp_u
     if rc:
         raise LookupError(f"MPIR_Hip_indexed_plan_info: {rc}")
     return dict(zip(("form", "launches", "groups", "per", "threshold", "rows_per_launch"), (int(v) for v in out)))
+
+
+# ---- ragged reductions (MPIX_Reduce_local_ragged)
+RAGGED_EMPTY, RAGGED_SINGLE, RAGGED_RAGGED = range(3)
+RAGGED_NAMES = ["empty", "single", "ragged"]
+
+
+def reduce_local_ragged(inbuf: int, in_displs, inoutbuf: int, inout_displs, starts, disp_unit: int, npieces: int,
+                        count: int, datatype: int, op: int, stream: int = 0) -> int:
+    """MPIX_Reduce_local_ragged: npieces pieces, piece k of starts[k + 1] -
+    starts[k] elements at inbuf + in_displs[k] * disp_unit and inoutbuf +
+    inout_displs[k] * disp_unit bytes (raw device addresses; a table None: that
+    side packed, piece k at starts[k] elements), in one launch.  starts has
+    npieces + 1 entries, from 0 to count.  Each table is a raw address or a numpy
+    int64 array (see _table_addr).  stream 0: synchronous on the library stream
+    (host tables allowed); otherwise enqueued on that HIP stream, no wait (device
+    tables only)."""
+    return load().MPIX_Reduce_local_ragged(ctypes.c_void_p(inbuf or None), ctypes.c_void_p(_table_addr(in_displs) or None),
+                                           ctypes.c_void_p(inoutbuf or None),
+                                           ctypes.c_void_p(_table_addr(inout_displs) or None),
+                                           ctypes.c_void_p(_table_addr(starts) or None), disp_unit, npieces, count,
+                                           datatype, op, ctypes.c_void_p(stream or None))
+
+
+def ragged_plan_info(inbuf: int, in_displs, inoutbuf: int, inout_displs, starts, disp_unit: int, npieces: int,
+                     count: int, datatype: int, op: int) -> dict:
+    """MPIR_Hip_ragged_plan_info: the launch of a ragged reduction of device
+    operands and tables at these addresses (never dereferenced, the tables only
+    compared with 0; no GPU needed): form (RAGGED_*), launches (1), groups, per
+    (packed elements per workgroup), rounds (of the wave-wide search for a
+    workgroup's first piece) and lds_entries (piece boundaries a workgroup holds in
+    LDS, 4 bytes each).  Raises LookupError where the pair has no kernel,
+    ValueError for arguments the call refuses."""
+    out = (ctypes.c_uint64 * 6)()
+    rc = load().MPIR_Hip_ragged_plan_info(ctypes.c_void_p(inbuf or None), ctypes.c_void_p(_table_addr(in_displs) or None),
+                                          ctypes.c_void_p(inoutbuf or None),
+                                          ctypes.c_void_p(_table_addr(inout_displs) or None),
+                                          ctypes.c_void_p(_table_addr(starts) or None), disp_unit, npieces, count,
+                                          op & 0xFF, _ELEM_BY_HANDLE[datatype], out)
+    if rc == MPIR_HIP_EARG:
+        raise ValueError("MPIR_Hip_ragged_plan_info: arguments refused")
+    if rc:
+        raise LookupError(f"MPIR_Hip_ragged_plan_info: {rc}")
+    return dict(zip(("form", "launches", "groups", "per", "rounds", "lds_entries"), (int(v) for v in out)))
 
 
 MPIX_HIP_ALG_AUTO = 0
