@@ -214,7 +214,7 @@ uint64_t MPIR_Hip_strided_test_max_groups(uint64_t groups);
  * undefined here (MPIX_Reduce_local_fetch refuses it).  hip_stream / sync as for
  * MPIR_Hip_reduce; the launch carries everything in its kernel arguments.
  * MPIR_HIP_ENOKERNEL for pairs with no kernel. */
-#define MPIR_HIP_OP_NO_OP 14   /* MPI_NO_OP's table index; MPIR_Hip_reduce_fetch alone takes it (no kernel table slot) */
+#define MPIR_HIP_OP_NO_OP 14   /* MPI_NO_OP's table index; MPIR_Hip_reduce_fetch and MPIR_Hip_reduce_fetch_ragged alone take it (no kernel table slot) */
 int MPIR_Hip_reduce_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, uint64_t count, int op, int elem,
                           void *hip_stream, int sync);
 
@@ -351,6 +351,63 @@ int MPIR_Hip_reduce_ragged(const void *inbuf, const int64_t *in_displs, void *in
 int MPIR_Hip_ragged_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
                               const int64_t *io_displs, const int64_t *starts, uint64_t disp_unit, uint64_t npieces,
                               uint64_t count, int op, int elem, uint64_t out[6]);
+
+/* Fetching ragged reduction: MPIR_Hip_reduce_fetch on a ragged target, the shape
+ * of the reference's MPI_Get_accumulate target handler
+ * (ch3u_handle_recv_req.c:326-358, :1391-1423: MPIR_Segment_pack of the
+ * derived-type target into the response buffer, :339-351, then do_accumulate_op
+ * over the same target, mpidrma.h:930-1021, "copy data + ACC needs to be
+ * atomic").  inbuf (the origin's streamed data) and fetchbuf (the response
+ * buffer) are packed; inoutbuf (the target) has the displacement table.  starts,
+ * disp_unit, npieces and count are MPIR_Hip_reduce_ragged's.  For piece k of
+ * len = starts[k + 1] - starts[k] elements at io_k = inoutbuf + io_displs[k] *
+ * disp_unit: the len * size bytes of fetchbuf at starts[k] * size receive the
+ * bytes io_k held on entry, a byte copy (never a value of the type), and io_k
+ * becomes what MPIR_Hip_reduce(inbuf + starts[k] * size, io_k, len) would leave,
+ * bit for bit.  ONE kernel launch always, which reads the target once: the value
+ * fetched and the value combined come from the same load of each target element.
+ * No byte outside the pieces is read or written, no byte of fetchbuf outside
+ * [0, count * size), no table.
+ * op: an MPIR_Hip_op MPIR_Hip_reduce_ragged has a kernel for, or
+ *   MPIR_HIP_OP_NO_OP    a pack: the pieces gathered into fetchbuf; inbuf is
+ *                        never looked at (it may be NULL), the target is not
+ *                        written;
+ *   MPIR_HIP_OP_REPLACE  a swap: the pieces out to fetchbuf, inbuf's bytes in;
+ * both byte operations with a kernel per element size, for every element class.
+ * The argument rules are MPIR_Hip_reduce_ragged's (disp_unit, count == 0,
+ * npieces, starts NULL beside a table: MPIR_HIP_EARG likewise), and so are the
+ * tables' residency and the checks of host tables (synchronous call on the
+ * library stream only, through the per-(thread, device) table buffer).
+ * io_displs NULL is MPIR_Hip_reduce_fetch on count elements; starts is not looked
+ * at.  Residency: inoutbuf's base, and the first and the last byte of fetchbuf's
+ * and (but for NO_OP) inbuf's count * size bytes, device memory on one device
+ * (else MPIR_HIP_EBUFFER).  Where both tables are host tables, the pieces'
+ * extremes are classified as MPIR_Hip_reduce_ragged does, and a fetchbuf range
+ * that meets any byte from the lowest piece's first to the highest piece's last
+ * is MPIR_HIP_EBUFFER.  With a device table fetchbuf overlapping a target piece
+ * is undefined; so is fetchbuf overlapping inbuf (MPIX_Reduce_local_fetch_ragged
+ * refuses that one).  Everything is checked before anything is enqueued, so a
+ * call that fails has written nothing.  With device tables the launch carries
+ * everything else in its kernel arguments (graph-capturable).
+ * A 16-byte chunk of packed space moves as one vector where it lies inside one
+ * piece and its three addresses are multiples of 16 (the packed two known on the
+ * host, the target's decided per chunk on the device); other chunks move element
+ * by element.  MPIR_HIP_ENOKERNEL for pairs with no kernel. */
+int MPIR_Hip_reduce_fetch_ragged(const void *inbuf, void *inoutbuf, const int64_t *io_displs, void *fetchbuf,
+                                 const int64_t *starts, uint64_t disp_unit, uint64_t npieces, uint64_t count, int op,
+                                 int elem, void *hip_stream, int sync);
+
+/* For tests and tools: the launch MPIR_Hip_reduce_fetch_ragged would make, from
+ * the same planner the launch runs (host arithmetic on the pointer values and
+ * counts only; no table is read, no GPU is needed).  out = {form (the
+ * MPIR_HIP_RAGGED_* forms), launches, workgroups, packed elements per workgroup,
+ * rounds of the wave-wide search, piece boundaries a workgroup holds in LDS, 1
+ * if the two packed sides are at multiples of 16 (NO_OP: fetchbuf alone) so that
+ * chunks can move as vectors}.  SINGLE reports MPIR_Hip_fetch_plan_info's grid as
+ * its workgroups and that call's launches (2 copies for REPLACE, else 1). */
+int MPIR_Hip_fetch_ragged_plan_info(const void *inbuf, const void *inoutbuf, const int64_t *io_displs,
+                                    const void *fetchbuf, const int64_t *starts, uint64_t disp_unit, uint64_t npieces,
+                                    uint64_t count, int op, int elem, uint64_t out[7]);
 
 /* Flags for the calling thread's later MPIR_Hip_combine calls; returns the
  * previous flags.  MPIR_HIP_COMBINE_UNCAPPED: the fused folds run without the

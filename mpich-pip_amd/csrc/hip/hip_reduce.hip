@@ -34,6 +34,8 @@ StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 RaggedEntry g_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+FetchRaggedEntry g_fetch_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+FetchRaggedEntry g_fetch_ragged_bytes[2][kFetchRaggedSizes];
 
 // Strided rows of at least this many bytes take the wide form (one row's tiles
 // per G workgroups), shorter ones the narrow form (rows flattened into units):
@@ -794,7 +796,8 @@ int ragged_host_products(const int64_t *displs, uint64_t disp_unit, uint64_t npi
 // signed bits MPIR_HIP_EARG).  Beside a device `starts` the lengths are the
 // kernel's to read, and only the products are checked.
 int ragged_host_extremes(const char *base, const int64_t *displs, const int64_t *host_starts, uint64_t disp_unit,
-                         uint64_t npieces, uint64_t esz, int dev) {
+                         uint64_t npieces, uint64_t esz, int dev, const char **first = nullptr,
+                         const char **last = nullptr) {
     int64_t lo = INT64_MAX, hi = INT64_MIN;     // first byte of the lowest, last byte of the highest
     for (uint64_t k = 0; k < npieces; ++k) {
         if (host_starts[k + 1] == host_starts[k]) continue;
@@ -811,7 +814,47 @@ int ragged_host_extremes(const char *base, const int64_t *displs, const int64_t 
         int d = -1;
         if (classify_in_span(ends[k], &d, span) != LOC_DEVICE || d != dev) return MPIR_HIP_EBUFFER;
     }
+    if (first) *first = base + lo;
+    if (last) *last = base + hi;
     return MPIR_HIP_OK;
+}
+
+// ---- fetching ragged calls.  The kernel of (op, elem): the pair's own, or for
+// the two byte ops the one of the element's size (null: none)
+fetch_ragged_fn fetch_ragged_kernel(int op, int elem) {
+    if (elem <= 0 || elem >= MPIR_HIP_NELEMS) return nullptr;
+    if (op == MPIR_HIP_OP_NO_OP || op == MPIR_HIP_OP_REPLACE) {
+        const uint64_t esz = g_elem_size[elem];
+        int l = 0;
+        while (l < kFetchRaggedSizes && ((uint64_t)1 << l) != esz) ++l;
+        return l < kFetchRaggedSizes ? g_fetch_ragged_bytes[op == MPIR_HIP_OP_REPLACE][l].launch : nullptr;
+    }
+    return pair_in_range(op, elem) ? g_fetch_ragged[op][elem].launch : nullptr;
+}
+
+// the argument checks MPIR_Hip_reduce_fetch_ragged makes before it looks at a
+// pointer: ragged_args' in ragged_args' order, with one table.  MPIR_HIP_OK with
+// *form EMPTY or SINGLE where that settles the call.
+int fetch_ragged_args(const void *io_displs, const void *starts, uint64_t disp_unit, uint64_t npieces, uint64_t count,
+                      int op, int elem, int *form) {
+    if (!fetch_ragged_kernel(op, elem)) return MPIR_HIP_ENOKERNEL;
+    if (!disp_unit || disp_unit > (~(uint64_t)0 >> 1)) return MPIR_HIP_EARG;
+    *form = MPIR_HIP_RAGGED_EMPTY;
+    if (!count) return MPIR_HIP_OK;
+    if (!npieces || npieces > (uint64_t)INT32_MAX || count > (uint64_t)INT32_MAX) return MPIR_HIP_EARG;
+    *form = MPIR_HIP_RAGGED_SINGLE;
+    if (!io_displs) return MPIR_HIP_OK;
+    if (!starts) return MPIR_HIP_EARG;
+    *form = MPIR_HIP_RAGGED_RAGGED;
+    return MPIR_HIP_OK;
+}
+
+// The two packed sides at multiples of 16 (NO_OP never looks at inbuf): what the
+// kernel is told, since a chunk's packed addresses are the bases plus a multiple
+// of 16 and need no table to know.
+bool fetch_ragged_packed_aligned(const void *in, const void *fetch, int op) {
+    const uintptr_t all = reinterpret_cast<uintptr_t>(fetch) | (op == MPIR_HIP_OP_NO_OP ? 0 : reinterpret_cast<uintptr_t>(in));
+    return (all & 15) == 0;
 }
 
 // the argument checks MPIR_Hip_reduce_fetch makes before it looks at a pointer;
@@ -1569,6 +1612,134 @@ int MPIR_Hip_reduce_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, uin
         if (e != hipSuccess) rc = set_err(e, "fetch launch");
         else if (sync) rc = wait_stream(dev, s);
     }
+    return rc;
+}
+
+int MPIR_Hip_fetch_ragged_plan_info(const void *inbuf, const void *inoutbuf, const int64_t *io_displs,
+                                    const void *fetchbuf, const int64_t *starts, uint64_t disp_unit, uint64_t npieces,
+                                    uint64_t count, int op, int elem, uint64_t out[7]) {
+    int form = 0;
+    const int rc = fetch_ragged_args(io_displs, starts, disp_unit, npieces, count, op, elem, &form);
+    if (rc != MPIR_HIP_OK) return rc;
+    for (int k = 0; k < 7; ++k) out[k] = 0;
+    out[0] = (uint64_t)form;
+    if (form == MPIR_HIP_RAGGED_EMPTY) return MPIR_HIP_OK;
+    if (form == MPIR_HIP_RAGGED_SINGLE) {
+        // the fetch call's own plan (MPIR_Hip_fetch_plan_info)
+        uint64_t f[4];
+        const int frc = MPIR_Hip_fetch_plan_info(inbuf, inoutbuf, fetchbuf, count, op, elem, f);
+        if (frc != MPIR_HIP_OK) return frc;
+        out[1] = f[0] == MPIR_HIP_FETCH_COPY && op == MPIR_HIP_OP_REPLACE ? 2 : 1;
+        out[2] = f[1];
+        return MPIR_HIP_OK;
+    }
+    RaggedPlan p;
+    ragged_plan(npieces, count, elem, p);
+    out[1] = 1;
+    out[2] = p.groups;
+    out[3] = p.per;
+    out[4] = p.rounds;
+    out[5] = p.lds_entries;
+    out[6] = fetch_ragged_packed_aligned(inbuf, fetchbuf, op);
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_reduce_fetch_ragged(const void *inbuf, void *inoutbuf, const int64_t *io_displs, void *fetchbuf,
+                                 const int64_t *starts, uint64_t disp_unit, uint64_t npieces, uint64_t count, int op,
+                                 int elem, void *hip_stream, int sync) {
+    int form = 0;
+    int rc = fetch_ragged_args(io_displs, starts, disp_unit, npieces, count, op, elem, &form);
+    if (rc != MPIR_HIP_OK || form == MPIR_HIP_RAGGED_EMPTY) return rc;
+    // no table: the fetch call, which makes its own checks; starts is not looked at
+    if (form == MPIR_HIP_RAGGED_SINGLE)
+        return MPIR_Hip_reduce_fetch(inbuf, inoutbuf, fetchbuf, count, op, elem, hip_stream, sync);
+    ctx().err[0] = 0;
+    // Everything is settled before anything is enqueued (a call that fails has
+    // written nothing), in MPIR_Hip_reduce_ragged's order.  First the tables:
+    // device memory, both ends, or, in a synchronous call on the library stream,
+    // host memory, which is then read for what is wrong with it (MPIR_HIP_EARG).
+    // Then residency: the three bases on one device (NO_OP never looks at inbuf),
+    // the last byte of the two packed sides, the device tables on that device;
+    // and, where both tables are host tables, the pieces' extremes and fetchbuf's
+    // range against the extent between them.
+    const uint64_t esz = g_elem_size[elem];
+    const bool no_op = op == MPIR_HIP_OP_NO_OP;
+    const int64_t *table[2] = {io_displs, starts};
+    const uint64_t entries[2] = {npieces, npieces + 1};
+    bool host_table[2] = {false, false};
+    int table_dev[2] = {-1, -1};
+    for (int k = 1; k >= 0; --k) {
+        DeviceSpan ts;
+        if (classify_in_span(table[k], &table_dev[k], ts) == LOC_DEVICE) {
+            int d2 = -1;
+            if (classify_in_span(reinterpret_cast<const char *>(table[k] + entries[k]) - 1, &d2, ts) != LOC_DEVICE ||
+                d2 != table_dev[k])
+                return MPIR_HIP_EBUFFER;
+            continue;
+        }
+        if (hip_stream || !sync) return MPIR_HIP_EBUFFER;       // a host table would be read after the call returned
+        host_table[k] = true;
+        rc = k == 1 ? ragged_host_starts(starts, npieces, count) : ragged_host_products(io_displs, disp_unit, npieces);
+        if (rc != MPIR_HIP_OK) return rc;
+    }
+    const char *in = static_cast<const char *>(inbuf);
+    char *io = static_cast<char *>(inoutbuf), *fe = static_cast<char *>(fetchbuf);
+    const uint64_t bytes = count * esz;
+    int dev = -1;
+    {
+        // io's base, then the packed sides' first and last bytes
+        const void *ends[5] = {io, fe, fe + (bytes - 1), in, in ? in + (bytes - 1) : in};
+        DeviceSpan span[3];
+        const int which[5] = {0, 1, 1, 2, 2};
+        for (int k = 0; k < (no_op ? 3 : 5); ++k) {
+            int d = -1;
+            if (classify_in_span(ends[k], &d, span[which[k]]) != LOC_DEVICE || (k && d != dev)) return MPIR_HIP_EBUFFER;
+            dev = d;
+        }
+    }
+    for (int k = 0; k < 2; ++k)
+        if (!host_table[k] && table_dev[k] != dev) return MPIR_HIP_EBUFFER;
+    if (host_table[0] && host_table[1]) {
+        const char *first = nullptr, *last = nullptr;
+        rc = ragged_host_extremes(io, io_displs, starts, disp_unit, npieces, esz, dev, &first, &last);
+        if (rc != MPIR_HIP_OK) return rc;
+        // the old bytes must not land on a piece: anywhere in the pieces' extent is refused
+        const uintptr_t f0 = reinterpret_cast<uintptr_t>(fe), f1 = f0 + (bytes - 1);
+        if (f0 <= reinterpret_cast<uintptr_t>(last) && reinterpret_cast<uintptr_t>(first) <= f1) return MPIR_HIP_EBUFFER;
+    }
+    const fetch_ragged_fn launch = fetch_ragged_kernel(op, elem);
+    DeviceScope on(dev);
+    if (!on.ok()) return on.err();
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!s) rc = get_stream(dev, S_MAIN, &s);
+    if (rc != MPIR_HIP_OK) return rc;
+    if (host_table[0] || host_table[1]) {
+        // host tables into the thread's table buffer, stream-ordered ahead of the
+        // kernel (the earlier synchronous call that read the buffer has returned)
+        size_t total = 0;
+        for (int k = 0; k < 2; ++k) total += host_table[k] ? (size_t)entries[k] * sizeof(int64_t) : 0;
+        char *buf = nullptr;
+        rc = get_tables(dev, total, &buf);
+        if (rc != MPIR_HIP_OK) return rc;               // (nothing of this call is queued yet)
+        for (int k = 0; k < 2; ++k) {
+            if (!host_table[k]) continue;
+            const size_t tbytes = (size_t)entries[k] * sizeof(int64_t);
+            const hipError_t ce = hipMemcpyAsync(buf, table[k], tbytes, hipMemcpyHostToDevice, s);
+            if (ce != hipSuccess) {
+                // (another table's copy may be queued on the library stream)
+                ctx().dev[dev].main_pending = true;
+                return set_err(ce, "fetch ragged table copy");
+            }
+            table[k] = reinterpret_cast<const int64_t *>(buf);
+            buf += tbytes;
+        }
+    }
+    const FetchRaggedArgs a{in, io, fe, table[0], table[1], disp_unit, (uint32_t)npieces, (uint32_t)count,
+                            (uint32_t)fetch_ragged_packed_aligned(in, fe, op), 0};
+    const hipError_t e = launch(&a, s);
+    if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
+    if (e != hipSuccess) rc = set_err(e, "fetch ragged launch");
+    else if (sync) rc = wait_stream(dev, s);
     return rc;
 }
 

@@ -38,6 +38,7 @@ typedef hipError_t (*fetch_fn)(const FetchArgs *, hipStream_t);
 typedef hipError_t (*indexed_fn)(const IndexedArgs *, uint64_t, hipStream_t);
 typedef hipError_t (*ragged_fn)(const RaggedArgs *, hipStream_t);
 typedef void (*fplan_fn)(const FetchArgs *, FetchPlan *);
+typedef hipError_t (*fetch_ragged_fn)(const FetchRaggedArgs *, hipStream_t);
 
 // plan: plan_reduce<T> (reduce_kernels.hpp) for the classes whose launcher is
 // launch_reduce -- the kernel, grid and argument bytes the direct AQL dispatch
@@ -72,6 +73,14 @@ struct IndexedEntry { indexed_fn launch; };
 // k_reduce_ragged (MPIR_Hip_reduce_ragged), for the pairs g_indexed holds
 // (reg_ragged<>, from the reg_ragged_*.hip units).
 struct RaggedEntry { ragged_fn launch; };
+// g_fetch_ragged[op][elem], likewise: launch_fetch_ragged<Op, T>, the one launch
+// of k_reduce_fetch_ragged (MPIR_Hip_reduce_fetch_ragged), for the pairs g_ragged
+// holds (reg_fetch_ragged<>, from the reg_fetch_ragged_*.hip units).
+// g_fetch_ragged_bytes[which][log2 size]: the same kernel over the two byte
+// functors, MPI_NO_OP (0) and MPI_REPLACE (1), one per element size from 1 to 32
+// bytes (reg_fetch_ragged_bytes.hip): they take every element class of that size.
+struct FetchRaggedEntry { fetch_ragged_fn launch; };
+constexpr int kFetchRaggedSizes = 6;
 
 // float / double SUM and PROD on the host: the SSE instruction itself.  The
 // reference's loop `a[i] = a[i] + b[i]` (opsum.c:21-76, gcc -O2) is an
@@ -144,6 +153,8 @@ extern StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern RaggedEntry g_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern FetchRaggedEntry g_fetch_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern FetchRaggedEntry g_fetch_ragged_bytes[2][kFetchRaggedSizes];
 constexpr int kMultiMaxP = 8;
 extern multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 
@@ -187,6 +198,18 @@ void reg_indexed(int op, int elem) {
 template <class Op, class T>
 void reg_ragged(int op, int elem) {
     g_ragged[op][elem] = RaggedEntry{&launch_ragged<Op, T>};
+}
+// the fetching ragged kernel of the same pairs, from the reg_fetch_ragged_*.hip units
+template <class Op, class T>
+void reg_fetch_ragged(int op, int elem) {
+    g_fetch_ragged[op][elem] = FetchRaggedEntry{&launch_fetch_ragged<Op, T>};
+}
+// ... and of MPI_NO_OP and MPI_REPLACE on elements of 1 << LOG2 bytes
+template <int LOG2>
+void reg_fetch_ragged_bytes() {
+    static_assert(LOG2 >= 0 && LOG2 < kFetchRaggedSizes, "element sizes 1 to 32 bytes");
+    g_fetch_ragged_bytes[0][LOG2] = FetchRaggedEntry{&launch_fetch_ragged<OpFetchNoOp, RawBytes<(1 << LOG2)>>};
+    g_fetch_ragged_bytes[1][LOG2] = FetchRaggedEntry{&launch_fetch_ragged<OpFetchSwap, RawBytes<(1 << LOG2)>>};
 }
 template <class Op, class T>
 void reg_multi(int op, int elem) {

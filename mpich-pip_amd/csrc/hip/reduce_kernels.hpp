@@ -1543,6 +1543,241 @@ hipError_t launch_fetch(const FetchArgs *a, hipStream_t s) {
 }
 
 // ============================================================================
+// Fetching ragged reductions (MPIR_Hip_reduce_fetch_ragged): the fetching
+// reduction on a ragged target -- the shape of the reference's MPI_Get_accumulate
+// target handler (ch3u_handle_recv_req.c:326-358, :1391-1423), which packs the
+// derived-type target into the contiguous response buffer (MPIR_Segment_pack,
+// :339-351) and then runs do_accumulate_op over the same target, piece by piece
+// against the packed origin data (mpidrma.h:930-1021), under "NOTE: 'copy data +
+// ACC' needs to be atomic".  in and fetch are packed (piece k at starts[k]
+// elements), io has the displacement table:
+//     fetch[starts[k] + i] = the bytes io_k[i] held,  io_k[i] = op(io_k[i], in[starts[k] + i])
+// with io_k = io + io_displs[k] * disp_unit, i < starts[k + 1] - starts[k].
+//
+// k_reduce_ragged's machinery unchanged (ragged_first_piece, the LDS boundary
+// passes, ragged_piece_lds / ragged_piece_far / ragged_bound / ragged_off) and
+// its division of work: workgroup g owns packed elements [g, g + 1) x kTileBytes
+// / sizeof(T), ragged_groups workgroups, one launch always.  One side has a
+// table, so LDS holds the boundaries (11 KiB) and one array of offsets (2 KiB).
+//
+//   * One read of io: the value stored to fetch and the value combined are the
+//     SAME registers, filled by one load of the target -- the vector x[j] of a
+//     vector chunk, the bytes `old` of fetch_ragged_elem.  The kernel holds no
+//     second load of io, as k_reduce_fetch holds none.
+//   * The fetched bytes are a byte copy (whole vectors, or an element's raw
+//     bytes; never a value of type T).
+//   * A 16-byte chunk of packed space inside one piece and not past count moves
+//     as a vector when its three byte addresses are multiples of 16.  The two
+//     packed ones are base + a multiple of 16, so the host decides them once
+//     (packed_aligned); the target's is decided here, per chunk.  A vector chunk
+//     is one nt 16-byte load of io, one of in, an nt store of io's registers to
+//     fetch and an nt store of combine16 to io.  No branch around the loads: a
+//     chunk that goes by elements loads the first 16 bytes of starts instead.
+//   * Every other chunk, and the 32-byte classes, element by element through
+//     fetch_ragged_elem, each element stepping forward to its own piece.
+//   * MPI_NO_OP and MPI_REPLACE are the byte functors OpFetchNoOp and
+//     OpFetchSwap over RawBytes<size>, one kernel per element SIZE: NO_OP loads
+//     no in and stores no io (a pack of the pieces into fetch), REPLACE stores
+//     in's bytes (a swap).
+//
+// 256 threads, 64 bytes of kernel arguments, 13 KiB of static LDS, no scratch,
+// no gridDim.
+// ============================================================================
+struct FetchRaggedArgs {
+    const char *in;             // packed; never looked at by OpFetchNoOp
+    char *io;                   // the target's base
+    char *fetch;                // packed
+    const int64_t *io_displs;   // npieces entries
+    const int64_t *starts;      // npieces + 1 entries
+    uint64_t disp_unit;         // bytes per displacement unit, > 0
+    uint32_t npieces;           // > 0
+    uint32_t count;             // packed elements, > 0
+    uint32_t packed_aligned;    // in (where it is read) and fetch are multiples of 16
+    uint32_t pad_;
+};
+
+static_assert(((uint64_t)INT32_MAX * 32 + kTileBytes - 1) / kTileBytes < kBatchMaxGroups,
+              "a fetching ragged reduction of INT_MAX elements must fit one launch");
+static_assert(kRaggedLdsEntries * sizeof(uint32_t) + kRaggedLdsOffsets * sizeof(uint64_t) == (13u << 10),
+              "13 KiB of static LDS: the boundaries and one side's offsets");
+
+// the two byte ops, and the element they move: size bytes of no type
+struct OpFetchNoOp {};
+struct OpFetchSwap {};
+template <int N>
+struct RawBytes { uint32_t __attribute__((ext_vector_type(N / 4))) v; };   // (one register value, no byte array)
+template <>
+struct RawBytes<1> { uint8_t v; };
+template <>
+struct RawBytes<2> { uint16_t v; };
+template <>
+struct RawBytes<4> { uint32_t v; };
+
+template <class Op, class T>
+__device__ __forceinline__ u32x4 fetch_ragged_combine16(u32x4 x, u32x4 y) {
+    if constexpr (__is_same(Op, OpFetchSwap)) return y;
+    else return combine16<Op, T>(x, y);
+}
+
+// one element: its bytes read once, stored to fetch as they are, then combined
+// (NO_OP: nothing more; REPLACE: in's bytes stored)
+template <class Op, class T>
+__device__ __forceinline__ void fetch_ragged_elem(const char *in, char *io, char *fetch) {
+    typedef RawBytes<(int)sizeof(T)> Raw;
+    Raw old;
+    __builtin_memcpy(&old, io, sizeof(T));
+    if constexpr (__is_same(Op, OpFetchNoOp)) {
+        __builtin_memcpy(fetch, &old, sizeof(T));
+    } else if constexpr (__is_same(Op, OpFetchSwap)) {
+        Raw y;
+        __builtin_memcpy(&y, in, sizeof(T));
+        __builtin_memcpy(fetch, &old, sizeof(T));
+        __builtin_memcpy(io, &y, sizeof(T));
+    } else {
+        Op op;
+        T y;
+        __builtin_memcpy(&y, in, sizeof(T));
+        __builtin_memcpy(fetch, &old, sizeof(T));
+        const T x = op(__builtin_bit_cast(T, old), y);
+        __builtin_memcpy(io, &x, sizeof(T));
+    }
+}
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_reduce_fetch_ragged(FetchRaggedArgs a) {
+    constexpr bool no_op = __is_same(Op, OpFetchNoOp);
+    constexpr uint32_t per = kTileBytes / sizeof(T);                    // the span's elements
+    constexpr uint32_t V = sizeof(T) <= 16 ? 16 / sizeof(T) : 1;        // a unit's elements
+    constexpr int per_lane = (int)(per / V / kThreads);
+    __shared__ uint32_t bnd[kRaggedLdsEntries];
+    __shared__ uint64_t off_io[kRaggedLdsOffsets];
+    const unsigned t = threadIdx.x;
+    const uint64_t e0 = (uint64_t)blockIdx.x * per;
+    if (e0 >= a.count) return;
+    RaggedSpan w;
+    w.starts = a.starts;
+    w.bnd = bnd;
+    w.off_in = nullptr;         // (the packed sides have no offsets)
+    w.off_io = off_io;
+    w.npieces = a.npieces;
+    w.e0 = (uint32_t)e0;
+    w.len = a.count - w.e0 < per ? a.count - w.e0 : per;
+    w.p0 = ragged_first_piece(a.starts, a.npieces, e0);
+    w.s0 = (int32_t)(a.starts[w.p0] - (int64_t)e0);
+    // the first 256 boundaries after starts[p0] and the byte offsets of pieces
+    // p0 ... p0 + 255, two loads at indices kept inside the tables, none behind
+    // a branch (k_reduce_ragged's first pass with one displacement side)
+    {
+        const uint64_t k = (uint64_t)w.p0 + t < a.npieces ? (uint64_t)w.p0 + t : a.npieces - 1;
+        const uint64_t m = (uint64_t)w.p0 + 1 + t;
+        const int64_t dj = a.io_displs[k];
+        int64_t v = a.starts[m <= a.npieces ? m : a.npieces] - (int64_t)e0;
+        v = m > a.npieces || v > (int64_t)w.len ? (int64_t)w.len : v < 0 ? 0 : v;
+        off_io[t] = (uint64_t)dj * a.disp_unit;
+        bnd[t] = (uint32_t)v;
+    }
+    w.nvalid = kThreads;
+    __syncthreads();
+    // further passes of 256 until a pass's last boundary has reached the span's end
+    while (bnd[w.nvalid - 1] < w.len && w.nvalid < kRaggedLdsEntries) {
+        const uint64_t m = (uint64_t)w.p0 + 1 + w.nvalid + t;
+        int64_t v = a.starts[m <= a.npieces ? m : a.npieces] - (int64_t)e0;
+        v = m > a.npieces || v > (int64_t)w.len ? (int64_t)w.len : v < 0 ? 0 : v;
+        bnd[w.nvalid + t] = (uint32_t)v;
+        w.nvalid += kThreads;
+        __syncthreads();
+    }
+
+    // bit j: the lane's unit j is still to do
+    uint32_t todo = 0;
+#pragma unroll
+    for (int j = 0; j < per_lane; ++j) todo |= (uint32_t)((t + (uint32_t)j * kThreads) * V < w.len) << j;
+    // the span's first byte on the two packed sides
+    const uint64_t pk0 = e0 * sizeof(T);
+
+    if constexpr (sizeof(T) <= 16) {
+        RaggedPiece p[per_lane];
+        uintptr_t po[per_lane];
+        u32x4 x[per_lane], y[per_lane];
+        bool vec[per_lane];
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) {
+            const uint32_t r = (t + (uint32_t)j * kThreads) * V;
+            // inside one piece (whose end is clipped to the span's, and so to count)
+            vec[j] = ragged_piece_lds(w, r < w.len ? r : w.len - 1, p[j]) && (todo >> j & 1) &&
+                     (int32_t)(r + V) <= p[j].e && a.packed_aligned;
+        }
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) po[j] = ragged_off(w, a.io_displs, off_io, a.disp_unit, p[j], sizeof(T));
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) {
+            const uint32_t r = (t + (uint32_t)j * kThreads) * V;
+            const uint64_t d = (uint64_t)(int64_t)((int32_t)r - p[j].s) * sizeof(T);    // bytes into the piece
+            po[j] += reinterpret_cast<uintptr_t>(a.io) + d;
+            vec[j] = vec[j] && (po[j] & 15) == 0;
+        }
+        // No branch around the loads (k_reduce_ragged's arrangement): a chunk that
+        // goes by elements loads the first 16 bytes of starts and drops them.
+        // x[j] is the ONE load of the target: it is stored to fetch and combined.
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) {
+            const uintptr_t spare = reinterpret_cast<uintptr_t>(a.starts);
+            const uint64_t pk = pk0 + (uint64_t)(t + (uint32_t)j * kThreads) * 16;
+            x[j] = __builtin_nontemporal_load(reinterpret_cast<const global_u32x4 *>(vec[j] ? po[j] : spare));
+            if constexpr (!no_op)
+                y[j] = __builtin_nontemporal_load(reinterpret_cast<const global_u32x4 *>(
+                    vec[j] ? reinterpret_cast<uintptr_t>(a.in) + pk : spare));
+        }
+#pragma unroll
+        for (int j = 0; j < per_lane; ++j) {
+            if (vec[j]) {
+                const uint64_t pk = pk0 + (uint64_t)(t + (uint32_t)j * kThreads) * 16;
+                __builtin_nontemporal_store(x[j], reinterpret_cast<global_u32x4 *>(reinterpret_cast<uintptr_t>(a.fetch) + pk));
+                if constexpr (!no_op)
+                    __builtin_nontemporal_store(fetch_ragged_combine16<Op, T>(x[j], y[j]),
+                                                reinterpret_cast<global_u32x4 *>(po[j]));
+                todo &= ~(1u << j);
+            }
+        }
+    }
+    // the other units, element by element: an element at or past its piece's end
+    // steps to the next piece that holds one (empty pieces fall through)
+#pragma unroll 1
+    for (uint32_t j = 0; j < (uint32_t)per_lane; ++j) {
+        if (!(todo >> j & 1)) continue;
+        const uint32_t r = (t + j * kThreads) * V;
+        RaggedPiece q;
+        if (!ragged_piece_lds(w, r, q)) ragged_piece_far(w, r, q);
+        uint64_t qo = ragged_off(w, a.io_displs, off_io, a.disp_unit, q, sizeof(T));
+        for (uint32_t i = 0; i < V && r + i < w.len; ++i) {
+            const int32_t e = (int32_t)(r + i);
+            if (e >= q.e) {
+                // (past the table every bound is the span's length, above e: the walk ends)
+                do {
+                    ++q.k;
+                    q.s = q.e;
+                    q.e = ragged_bound(w, (uint64_t)q.k + 1);
+                } while (e >= q.e);
+                qo = ragged_off(w, a.io_displs, off_io, a.disp_unit, q, sizeof(T));
+            }
+            const uint64_t pk = pk0 + (uint64_t)(uint32_t)e * sizeof(T);
+            fetch_ragged_elem<Op, T>(a.in + pk, a.io + qo + (uint64_t)(int64_t)(e - q.s) * sizeof(T), a.fetch + pk);
+        }
+    }
+}
+
+// one launch, always: the grid is the packed elements' spans
+template <class Op, class T>
+hipError_t launch_fetch_ragged(const FetchRaggedArgs *a, hipStream_t s) {
+    const uint64_t groups = ragged_groups(a->count, sizeof(T));
+    if (!a->npieces || !a->count || !a->disp_unit || !a->starts || !a->io_displs || groups < 1 ||
+        groups > kBatchMaxGroups)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_reduce_fetch_ragged<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+// ============================================================================
 // Multi-operand combines: the log2(p) / (p-1) MPIR_Reduce_local steps of a
 // reduction schedule fused into ONE pass over HBM, in the schedule's exact
 // association and operand order (so results are bit-identical to running the

@@ -117,6 +117,7 @@ EXPORTED_SYMBOLS = [
     "MPIX_Reduce_local_fetch", "MPIR_Hip_reduce_fetch", "MPIR_Hip_fetch_plan_info",
     "MPIX_Reduce_local_indexed", "MPIR_Hip_reduce_indexed", "MPIR_Hip_indexed_plan_info",
     "MPIX_Reduce_local_ragged", "MPIR_Hip_reduce_ragged", "MPIR_Hip_ragged_plan_info",
+    "MPIX_Reduce_local_fetch_ragged", "MPIR_Hip_reduce_fetch_ragged", "MPIR_Hip_fetch_ragged_plan_info",
     # device collectives (include/mpix_hip_coll.h)
     "MPIX_Hip_comm_get_unique_id", "MPIX_Hip_comm_create", "MPIX_Hip_comm_create_loopback",
     "MPIX_Hip_comm_free", "MPIX_Hip_comm_rank", "MPIX_Hip_comm_size",
@@ -214,6 +215,12 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.MPIR_Hip_reduce_ragged.restype = i32
     lib.MPIR_Hip_ragged_plan_info.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, ctypes.POINTER(u64)]
     lib.MPIR_Hip_ragged_plan_info.restype = i32
+    lib.MPIX_Reduce_local_fetch_ragged.argtypes = [vp, vp, vp, vp, vp, ctypes.c_long, i32, i32, i32, i32, vp]
+    lib.MPIX_Reduce_local_fetch_ragged.restype = i32
+    lib.MPIR_Hip_reduce_fetch_ragged.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, vp, i32]
+    lib.MPIR_Hip_reduce_fetch_ragged.restype = i32
+    lib.MPIR_Hip_fetch_ragged_plan_info.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, ctypes.POINTER(u64)]
+    lib.MPIR_Hip_fetch_ragged_plan_info.restype = i32
     lib.MPIX_Hip_comm_get_unique_id.argtypes = [vp]
     lib.MPIX_Hip_comm_get_unique_id.restype = i32
     lib.MPIX_Hip_comm_create.argtypes = [vp, i32, i32, ctypes.POINTER(vp)]
@@ -624,6 +631,49 @@ def ragged_plan_info(inbuf: int, in_displs, inoutbuf: int, inout_displs, starts,
     if rc:
         raise LookupError(f"MPIR_Hip_ragged_plan_info: {rc}")
     return dict(zip(("form", "launches", "groups", "per", "rounds", "lds_entries"), (int(v) for v in out)))
+
+
+# ---- fetching ragged reductions (MPIX_Reduce_local_fetch_ragged)
+def reduce_local_fetch_ragged(inbuf: int, inoutbuf: int, inout_displs, fetchbuf: int, starts, disp_unit: int,
+                              npieces: int, count: int, datatype: int, op: int, stream: int = 0) -> int:
+    """MPIX_Reduce_local_fetch_ragged: the fetching reduction on a ragged target.
+    inbuf and fetchbuf are packed (piece k at starts[k] elements), piece k of the
+    target is at inoutbuf + inout_displs[k] * disp_unit bytes (raw device
+    addresses): fetchbuf receives the bytes the pieces held, the pieces the
+    combine, in one launch that reads the target once.  MPI_NO_OP (a pack; inbuf
+    may be 0) and MPI_REPLACE (a swap) are accepted.  inout_displs None: the fetch
+    call on count elements.  Each table is a raw address or a numpy int64 array
+    (see _table_addr).  stream 0: synchronous on the library stream (host tables
+    allowed); otherwise enqueued on that HIP stream, no wait (device tables only)."""
+    return load().MPIX_Reduce_local_fetch_ragged(ctypes.c_void_p(inbuf or None), ctypes.c_void_p(inoutbuf or None),
+                                                 ctypes.c_void_p(_table_addr(inout_displs) or None),
+                                                 ctypes.c_void_p(fetchbuf or None),
+                                                 ctypes.c_void_p(_table_addr(starts) or None), disp_unit, npieces,
+                                                 count, datatype, op, ctypes.c_void_p(stream or None))
+
+
+def fetch_ragged_plan_info(inbuf: int, inoutbuf: int, inout_displs, fetchbuf: int, starts, disp_unit: int,
+                           npieces: int, count: int, datatype: int, op: int) -> dict:
+    """MPIR_Hip_fetch_ragged_plan_info: the launch of a fetching ragged reduction of
+    device operands and tables at these addresses (never dereferenced, the tables
+    only compared with 0; no GPU needed): form (RAGGED_*), launches, groups, per
+    (packed elements per workgroup), rounds (of the wave-wide search), lds_entries
+    (piece boundaries a workgroup holds in LDS) and packed_sides_aligned (1: inbuf
+    and fetchbuf at multiples of 16, so chunks can move as vectors).  Raises
+    LookupError where the pair has no kernel, ValueError for arguments the call
+    refuses."""
+    out = (ctypes.c_uint64 * 7)()
+    rc = load().MPIR_Hip_fetch_ragged_plan_info(ctypes.c_void_p(inbuf or None), ctypes.c_void_p(inoutbuf or None),
+                                                ctypes.c_void_p(_table_addr(inout_displs) or None),
+                                                ctypes.c_void_p(fetchbuf or None),
+                                                ctypes.c_void_p(_table_addr(starts) or None), disp_unit, npieces,
+                                                count, op & 0xFF, _ELEM_BY_HANDLE[datatype], out)
+    if rc == MPIR_HIP_EARG:
+        raise ValueError("MPIR_Hip_fetch_ragged_plan_info: arguments refused")
+    if rc:
+        raise LookupError(f"MPIR_Hip_fetch_ragged_plan_info: {rc}")
+    return dict(zip(("form", "launches", "groups", "per", "rounds", "lds_entries", "packed_sides_aligned"),
+                    (int(v) for v in out)))
 
 
 MPIX_HIP_ALG_AUTO = 0
