@@ -374,7 +374,9 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_fetch(const void *inbuf, void *inoutbuf, 
  *   Displacements may be negative.  A repeated in_displs entry is fine (input
  *       is only read).  Output blocks that overlap each other, or an input
  *       block, are undefined and not checked: MPI forbids overlapping target
- *       entries in an accumulate, and the blocks run concurrently.
+ *       entries in an accumulate, and the blocks run concurrently.  A table with
+ *       repeated targets (embedding rows hit twice, several accumulates queued
+ *       to one location) is MPIX_Reduce_local_indexed_ordered's.
  *   Ops and types as the strided call validates them, in its order: MPI_REPLACE,
  *       MPI_NO_OP, null, invalid and user ops, and MPI_LAND / MPI_LOR on
  *       floating types: MPI_ERR_OP; nblocks < 0 or blocklen < 0: MPI_ERR_COUNT;
@@ -416,6 +418,89 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_fetch(const void *inbuf, void *inoutbuf, 
 MPICH_API_PUBLIC int MPIX_Reduce_local_indexed(const void *inbuf, const MPI_Aint * in_displs,
                               void *inoutbuf, const MPI_Aint * inout_displs, MPI_Aint disp_unit,
                               int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream);
+/* Ordered indexed local reduction: MPIX_Reduce_local_indexed whose output table
+ * may name the same block any number of times -- a scatter-add with repeated
+ * rows (embedding gradients), many contributions assembled into one node, or the
+ * accumulates an RMA target has queued for one location, which MPI orders
+ * (MPI-3.1 11.7.2, accumulate_ordering).  The call is exactly
+ *   for k = 0 .. nblocks - 1, one after another in that order:
+ *     MPI_Reduce_local((char *) inbuf + in_off(k), (char *) inoutbuf + io_off(k),
+ *                      blocklen, datatype, op)
+ * bit for bit (in_off, io_off: the indexed call's), deterministic where atomics
+ * are not; each distinct target block is read once and written once, however
+ * many contributions it gets.  No byte outside the blocks is read or written,
+ * and no table is written.
+ *   Two output blocks must have equal inout_displs entries or be disjoint;
+ *       partial overlap stays undefined, as does an input block that overlaps
+ *       an output block.
+ *   order has nblocks ints and puts the blocks of one target side by side: a
+ *       permutation of [0, nblocks) such that inout_displs[order[p]] is
+ *       non-decreasing in p and, within equal displacements, order[p] is
+ *       ascending (ties keep table order).  That is a stable argsort of
+ *       inout_displs by signed value; any framework's will do, and
+ *       MPIX_Reduce_local_order makes one.  Build it once per index pattern and
+ *       combine many times.
+ *   order NULL is a promise of no repeats: the call is
+ *       MPIX_Reduce_local_indexed unchanged.  order with inout_displs NULL is
+ *       MPI_ERR_ARG: a packed target has no repeats.
+ *   Validation is the indexed call's, in its order: ops (MPI_REPLACE and
+ *       MPI_NO_OP stay MPI_ERR_OP), counts, MPI_IN_PLACE, the alias check,
+ *       disp_unit; either count 0 succeeds and looks at no pointer.
+ *   Bases and tables have the indexed call's residency rules, order a third
+ *       table under them: device memory on the operands' device, or, with
+ *       hip_stream NULL, host memory (with a stream: MPI_ERR_BUFFER).  A host
+ *       order is checked: every entry in range, none twice, and, where
+ *       inout_displs is a host table too, the two ordering conditions
+ *       (MPI_ERR_ARG).  A device order that breaks its conditions is the
+ *       caller's error and the result is undefined; the kernel still clamps
+ *       every index it reads from it, so its reads of all three tables stay
+ *       inside them.
+ *   A call that returns an error has written nothing.
+ *   hip_stream as in the indexed call; with device tables everything travels in
+ *       the kernel arguments: nothing is allocated, no library scratch is used,
+ *       and the call can be captured into a graph.
+ *   The blocks of one target are folded serially by one slice of one workgroup
+ *       (one lane per 16 bytes of a narrow block, one workgroup per 16 KiB tile
+ *       of a wide one): the order is the contract, and a tree would change
+ *       floating-point results.  A hot row costs time in proportion to its
+ *       contributions; distinct targets run concurrently.
+ *   Measured: fp32 MPI_SUM, medians of alternated rounds (Ordered
+ *       indexed reductions, has the table).  65,536 blocks of 256 bytes: with
+ *       no repeats 22.7 us against the indexed call's 19.2 (1.18 x: the order
+ *       entry and the neighbours' displacements are read before any data); 4
+ *       blocks per target 36 us against 51 for four duplicate-free rounds of
+ *       the indexed call, 64 per target 52 us against 745.  4096 blocks of 64
+ *       KiB: 142 us against the indexed call's 162 with no repeats, 97 against
+ *       196 at 4 per target, 340 against 840 at 64.  A hot row: all 65,536
+ *       blocks of 256 bytes on one target take 29 ms (0.44 us a contribution),
+ *       all 4096 of 64 KiB 4.2 ms (1 us): keep such a row out of the table, or
+ *       pre-reduce it, where the order of its sum may be chosen.
+ *       MPIX_Reduce_local_order: 56 us for 65,536 entries, 31 us for 4096. */
+MPICH_API_PUBLIC int MPIX_Reduce_local_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs,
+                              void *inoutbuf, const MPI_Aint * inout_displs, const int *order,
+                              MPI_Aint disp_unit, int nblocks, int blocklen,
+                              MPI_Datatype datatype, MPI_Op op, void *hip_stream);
+/* The order table of a displacement table, for MPIX_Reduce_local_indexed_ordered:
+ * order[p] = the block at sorted position p, a stable sort of (displs[k], k) by
+ * the signed displacement.  nblocks < 0: MPI_ERR_COUNT; nblocks 0 succeeds and
+ * looks at nothing.
+ *   work is scratch of at least MPIX_Reduce_local_order_worksize(nblocks) bytes
+ *       in device memory on the device of displs (fewer work_bytes:
+ *       MPI_ERR_ARG); no byte past that size is touched.  With hip_stream NULL
+ *       work may be NULL and the library uses a buffer of its own; with a
+ *       stream a NULL work is MPI_ERR_BUFFER.  The size depends on nblocks
+ *       alone, never decreases with it, and needs no GPU to ask.
+ *   displs and order in device memory: the build is enqueued on the stream, or
+ *       synchronous when hip_stream is NULL.  A synchronous call also takes
+ *       either table in host memory (copied through the library's table
+ *       buffer); with both on the host it is a host stable sort and the GPU
+ *       runtime is not opened.  A host table with a stream is MPI_ERR_BUFFER.
+ *   The build makes several launches, their number depending on nblocks, and
+ *       asks the runtime about the device: capture into a graph is NOT promised.
+ *       Build outside the capture, and capture the combine. */
+MPICH_API_PUBLIC int MPIX_Reduce_local_order_worksize(int nblocks, MPI_Aint * work_bytes);
+MPICH_API_PUBLIC int MPIX_Reduce_local_order(const MPI_Aint * displs, int nblocks, int *order,
+                              void *work, MPI_Aint work_bytes, void *hip_stream);
 /* Ragged local reduction: many pieces of unequal length in one launch -- the
  * target of an accumulate on an MPI_Type_indexed / MPI_Type_create_hindexed
  * type, a sub-array with a ragged edge, any list of (location, length) pieces
@@ -435,7 +520,8 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_indexed(const void *inbuf, const MPI_Aint
  *   disp_unit, NULL tables, signed displacements, repeated input pieces and
  *       overlapping output pieces (undefined, not checked) are as in
  *       MPIX_Reduce_local_indexed.  Both tables NULL is the single call on count
- *       elements, and starts is not looked at.
+ *       elements, and starts is not looked at.  Equal pieces whose targets
+ *       repeat are MPIX_Reduce_local_indexed_ordered's.
  *   Ops and types as the indexed call validates them, in its order; npieces < 0
  *       or count < 0: MPI_ERR_COUNT; MPI_IN_PLACE: MPI_ERR_BUFFER; inbuf ==
  *       inoutbuf: MPI_ERR_BUFFER under MPIR_CVAR_COLL_ALIAS_CHECK; disp_unit <=

@@ -56,7 +56,7 @@ enum MPIR_Hip_elem {
 #define MPIR_HIP_ERUNTIME  2   /* HIP runtime failure; see MPIR_Hip_error_string() */
 #define MPIR_HIP_ENOKERNEL 3   /* (op, elem) pair has no kernel */
 #define MPIR_HIP_ENODEV    4   /* no usable GPU */
-#define MPIR_HIP_EARG      5   /* an argument out of range (MPIR_Hip_reduce_strided's strides, MPIR_Hip_reduce_indexed's and MPIR_Hip_reduce_ragged's disp_unit, offsets and tables) */
+#define MPIR_HIP_EARG      5   /* an argument out of range (MPIR_Hip_reduce_strided's strides, MPIR_Hip_reduce_indexed's and MPIR_Hip_reduce_ragged's disp_unit, offsets and tables, MPIR_Hip_reduce_indexed_ordered's order table, MPIR_Hip_order_build's work_bytes) */
 
 /* Combine inoutbuf[i] = op(inoutbuf[i], inbuf[i]) for i < count elements of
  * class `elem`.  Pointers may be device, pinned-host or pageable-host memory
@@ -292,6 +292,68 @@ int MPIR_Hip_reduce_indexed(const void *inbuf, const int64_t *in_displs, void *i
 int MPIR_Hip_indexed_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
                                const int64_t *io_displs, uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen,
                                int op, int elem, uint64_t out[6]);
+
+/* Ordered indexed reduction: MPIR_Hip_reduce_indexed whose output table may name
+ * one block any number of times, with the result of the blocks applied one after
+ * another in table order: for k = 0 .. nblocks - 1 in that order, io_k[i] =
+ * op(io_k[i], in_k[i]), bit-identical to that sequence of MPIR_Hip_reduce calls.
+ * Two output blocks must have equal io_displs entries or be disjoint (partial
+ * overlap is undefined, as is an input block that overlaps an output block).
+ * `order` (nblocks ints) puts the blocks of one target side by side: a
+ * permutation of [0, nblocks) with io_displs[order[p]] non-decreasing in p and,
+ * within equal displacements, order[p] ascending -- a stable argsort of
+ * io_displs, which MPIR_Hip_order_build makes.  The kernel
+ * (k_reduce_indexed_ordered, reduce_kernels.hpp) gives each run of equal
+ * displacements to the workgroups (WIDE) or lanes (NARROW) of its first sorted
+ * position, which load the target once, fold the run's input blocks into
+ * registers serially, in order, and store once; the plan, the forms, the
+ * threshold and the per-launch cap are the indexed call's, rows read as sorted
+ * positions.  Later launches get the same tables and bases with their first
+ * position: a run may cross a launch boundary and still has one owner.
+ * order NULL is MPIR_Hip_reduce_indexed unchanged (a promise of no repeats).
+ * Otherwise the indexed call's argument checks, then io_displs NULL or nblocks >
+ * INT32_MAX: MPIR_HIP_EARG (counts of 0 succeed before that, no pointer looked
+ * at).  Residency as the indexed call's, `order` a third table under the same
+ * rules.  A host order table is checked (MPIR_HIP_EARG): every entry in range,
+ * no entry twice and, where io_displs is a host table too, the two ordering
+ * conditions.  A device order table is not, and one that breaks the conditions
+ * gives an undefined result; every index the kernel reads from it is clamped
+ * into [0, nblocks), so its reads of all three tables stay inside them.
+ * A call that fails has written nothing; no table is ever written.  With device
+ * tables the launch carries everything in its kernel arguments (no library
+ * buffer, graph-capturable). */
+int MPIR_Hip_reduce_indexed_ordered(const void *inbuf, const int64_t *in_displs, void *inoutbuf,
+                                    const int64_t *io_displs, const int *order, uint64_t disp_unit, uint64_t nblocks,
+                                    uint64_t blocklen, int op, int elem, void *hip_stream, int sync);
+
+/* For tests and tools: MPIR_Hip_indexed_plan_info's six outputs for the launches
+ * MPIR_Hip_reduce_indexed_ordered would make (rows are sorted positions; `order`
+ * is only compared with NULL).  Returns as that call does, residency apart. */
+int MPIR_Hip_indexed_ordered_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
+                                       const int64_t *io_displs, const int *order, uint64_t disp_unit,
+                                       uint64_t nblocks, uint64_t blocklen, int op, int elem, uint64_t out[6]);
+
+/* The order table of `displs` (nblocks signed 64-bit displacements): order[p]
+ * the block at sorted position p, a stable sort by displacement.
+ * *work_bytes = the scratch MPIR_Hip_order_build may use for nblocks, from
+ * nblocks alone (host arithmetic, non-decreasing, no GPU needed): room for the
+ * sorted keys plus a bound on what rocPRIM's radix_sort_pairs asks for on any
+ * device.  nblocks > INT32_MAX: MPIR_HIP_EARG (both functions).
+ * Build: both tables device memory on one device: the sort is enqueued on
+ * hip_stream, or on the library stream and waited for with sync != 0 and
+ * hip_stream NULL.  `work` is device memory there of at least *work_bytes
+ * (work_bytes less: MPIR_HIP_EARG; not device memory: MPIR_HIP_EBUFFER); bytes
+ * past the reported size are never touched.  work NULL without a stream: the
+ * thread's table buffer serves; with a stream: MPIR_HIP_EBUFFER.  In a
+ * synchronous call either table may be host memory (with a stream:
+ * MPIR_HIP_EBUFFER): both on the host is a host stable sort that does not open
+ * the GPU runtime; one of them is copied through the table buffer.  nblocks 0
+ * succeeds and looks at nothing.  The build allocates nothing on a stream but
+ * makes several launches whose number depends on nblocks, and asks the runtime
+ * for the device's properties: capture into a graph is not promised. */
+int MPIR_Hip_order_worksize(uint64_t nblocks, uint64_t *work_bytes);
+int MPIR_Hip_order_build(const int64_t *displs, uint64_t nblocks, int *order, void *work, uint64_t work_bytes,
+                         void *hip_stream, int sync);
 
 /* Ragged reduction: npieces pieces of unequal length.  starts (npieces + 1
  * entries) holds the pieces' element offsets in packed order, CSR row pointers:

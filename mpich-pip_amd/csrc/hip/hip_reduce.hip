@@ -15,7 +15,9 @@
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <mutex>
+#include <new>
 
 #include "mpir_hip_reduce.h"
 #include "kernel_table.hpp"
@@ -32,6 +34,7 @@ multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+OrderedEntry g_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 RaggedEntry g_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchRaggedEntry g_fetch_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
@@ -736,6 +739,74 @@ int indexed_host_table(const char *base, const int64_t *displs, uint64_t disp_un
     return MPIR_HIP_OK;
 }
 
+// ---- ordered indexed calls: the indexed call's plan over sorted positions.
+// the argument checks MPIR_Hip_reduce_indexed_ordered makes before it looks at
+// a pointer, for a call with an order table: the indexed call's, then the two of
+// its own (an order table needs an output table to sort, and holds ints)
+int ordered_args(const void *in_displs, const void *io_displs, uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen,
+                 int op, int elem, int *form) {
+    if (!pair_in_range(op, elem) || !g_ordered[op][elem].launch) return MPIR_HIP_ENOKERNEL;
+    const int rc = indexed_args(in_displs, io_displs, disp_unit, nblocks, blocklen, op, elem, form);
+    if (rc != MPIR_HIP_OK || *form == MPIR_HIP_INDEXED_EMPTY) return rc;
+    if (!io_displs || nblocks > (uint64_t)INT32_MAX) return MPIR_HIP_EARG;
+    return MPIR_HIP_OK;
+}
+
+// The launches of an ordered plan: later ranges of sorted positions.  The bases
+// and the tables are the call's in every launch (a head test looks back and a
+// run goes on across a launch boundary); the range is in pos0 and nrows.
+template <class F>
+void ordered_launches(const StridedPlan &p, const void *in, const int64_t *in_displs, void *io,
+                      const int64_t *io_displs, const int *order, uint64_t disp_unit, uint64_t nblocks,
+                      uint64_t blocklen, F emit) {
+    for (uint64_t pos0 = 0; pos0 < nblocks; pos0 += p.rows_per_launch) {
+        const uint64_t n = std::min(p.rows_per_launch, nblocks - pos0);
+        const OrderedArgs a{static_cast<const char *>(in), static_cast<char *>(io), in_displs, io_displs, order,
+                            disp_unit, blocklen, (uint32_t)nblocks, (uint32_t)pos0, (uint32_t)n, (uint32_t)p.form,
+                            (uint32_t)(p.form == MPIR_HIP_INDEXED_WIDE ? p.per : p.upr), 0};
+        if (!emit(a, strided_launch_groups(p, n))) return;
+    }
+}
+
+// A host order table, read before anything is enqueued: a permutation of
+// [0, nblocks), and, where the output table is host memory too (else null), its
+// displacements non-decreasing along it with ties in ascending block number.
+// MPIR_HIP_EARG otherwise.
+int ordered_host_order(const int *order, const int64_t *io_displs, uint64_t nblocks) {
+    std::unique_ptr<uint8_t[]> seen(new (std::nothrow) uint8_t[nblocks]());
+    if (!seen) {
+        snprintf(ctx().err, sizeof(ctx().err), "no memory to check an order table of %llu entries",
+                 (unsigned long long)nblocks);
+        return MPIR_HIP_ERUNTIME;
+    }
+    for (uint64_t p = 0; p < nblocks; ++p) {
+        const int k = order[p];
+        if (k < 0 || (uint64_t)k >= nblocks || seen[k]) return MPIR_HIP_EARG;
+        seen[k] = 1;
+    }
+    if (io_displs)
+        for (uint64_t p = 1; p < nblocks; ++p) {
+            const int64_t a = io_displs[order[p - 1]], b = io_displs[order[p]];
+            if (a > b || (a == b && order[p - 1] > order[p])) return MPIR_HIP_EARG;
+        }
+    return MPIR_HIP_OK;
+}
+
+// both ends of a table of `bytes` at t: device memory on `dev` (*dev < 0: any
+// device, which it then names)?  false: host memory; MPIR_HIP_EBUFFER in *rc
+// where it starts on a device and is not all on the one
+bool table_on_device(const void *t, uint64_t bytes, int *dev, int *rc) {
+    DeviceSpan ts;
+    int d = -1, d2 = -1;
+    *rc = MPIR_HIP_OK;
+    if (classify_in_span(t, &d, ts) != LOC_DEVICE) return false;
+    if ((*dev >= 0 && d != *dev) ||
+        classify_in_span(static_cast<const char *>(t) + (bytes - 1), &d2, ts) != LOC_DEVICE || d2 != d)
+        *rc = MPIR_HIP_EBUFFER;
+    *dev = d;
+    return true;
+}
+
 // ---- ragged calls: unequal pieces from a table of packed element offsets.
 // the argument checks MPIR_Hip_reduce_ragged makes before it looks at a pointer;
 // MPIR_HIP_OK with *form EMPTY or SINGLE where that settles the call
@@ -1422,6 +1493,198 @@ int MPIR_Hip_reduce_indexed(const void *inbuf, const int64_t *in_displs, void *i
     if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
     if (e != hipSuccess) rc = set_err(e, "indexed launch");
     else if (sync) rc = wait_stream(dev, s);
+    return rc;
+}
+
+int MPIR_Hip_indexed_ordered_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
+                                       const int64_t *io_displs, const int *order, uint64_t disp_unit,
+                                       uint64_t nblocks, uint64_t blocklen, int op, int elem, uint64_t out[6]) {
+    if (!order)
+        return MPIR_Hip_indexed_plan_info(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, op, elem,
+                                          out);
+    int form = 0;
+    const int rc = ordered_args(in_displs, io_displs, disp_unit, nblocks, blocklen, op, elem, &form);
+    if (rc != MPIR_HIP_OK) return rc;
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    out[0] = (uint64_t)form;
+    out[4] = mpir_hip::g_strided_wide.load(std::memory_order_relaxed);
+    if (form == MPIR_HIP_INDEXED_EMPTY) return MPIR_HIP_OK;
+    StridedPlan p;
+    indexed_plan(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, elem, p);
+    out[0] = (uint64_t)p.form;
+    out[1] = p.launches;
+    out[2] = p.groups;
+    out[3] = p.per;
+    out[5] = p.rows_per_launch;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_reduce_indexed_ordered(const void *inbuf, const int64_t *in_displs, void *inoutbuf,
+                                    const int64_t *io_displs, const int *order, uint64_t disp_unit, uint64_t nblocks,
+                                    uint64_t blocklen, int op, int elem, void *hip_stream, int sync) {
+    // no order table: a promise of no repeats, the indexed call unchanged
+    if (!order)
+        return MPIR_Hip_reduce_indexed(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, op, elem,
+                                       hip_stream, sync);
+    int form = 0;
+    int rc = ordered_args(in_displs, io_displs, disp_unit, nblocks, blocklen, op, elem, &form);
+    if (rc != MPIR_HIP_OK || form == MPIR_HIP_INDEXED_EMPTY) return rc;
+    ctx().err[0] = 0;
+    // everything classified before anything is enqueued, as the indexed call
+    // does: both bases, the last byte of a packed input, and the three tables --
+    // device memory on the operands' device or, in a synchronous call on the
+    // library stream, host memory, which is then read and checked
+    const uint64_t row_bytes = blocklen * g_elem_size[elem];
+    const char *base[2] = {static_cast<const char *>(inbuf), static_cast<char *>(inoutbuf)};
+    const void *table[3] = {in_displs, io_displs, order};
+    const size_t tbytes[3] = {(size_t)nblocks * sizeof(int64_t), (size_t)nblocks * sizeof(int64_t),
+                              (size_t)nblocks * sizeof(int)};
+    bool host_table[3] = {false, false, false};
+    int dev = -1;
+    DeviceSpan span[2];
+    for (int k = 0; k < 2; ++k) {
+        int d = -1;
+        if (classify_in_span(base[k], &d, span[k]) != LOC_DEVICE || (k && d != dev)) return MPIR_HIP_EBUFFER;
+        dev = d;
+        if (!table[k] &&
+            (classify_in_span(base[k] + (nblocks * row_bytes - 1), &d, span[k]) != LOC_DEVICE || d != dev))
+            return MPIR_HIP_EBUFFER;
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (!table[k]) continue;
+        if (table_on_device(table[k], tbytes[k], &dev, &rc)) {
+            if (rc != MPIR_HIP_OK) return rc;
+            continue;
+        }
+        if (hip_stream || !sync) return MPIR_HIP_EBUFFER;       // a host table would be read after the call returned
+        host_table[k] = true;
+        if (k < 2) rc = indexed_host_table(base[k], static_cast<const int64_t *>(table[k]), disp_unit, nblocks, row_bytes, dev);
+        else rc = ordered_host_order(order, host_table[1] ? io_displs : nullptr, nblocks);
+        if (rc != MPIR_HIP_OK) return rc;
+    }
+    StridedPlan p;
+    indexed_plan(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, elem, p);
+    if (p.form == MPIR_HIP_INDEXED_WIDE && p.per > kBatchMaxGroups) {
+        snprintf(ctx().err, sizeof(ctx().err), "an indexed block needs more workgroups than one launch holds");
+        return MPIR_HIP_ERUNTIME;
+    }
+    DeviceScope on(dev);
+    if (!on.ok()) return on.err();
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!s) rc = get_stream(dev, S_MAIN, &s);
+    if (rc != MPIR_HIP_OK) return rc;
+    if (host_table[0] || host_table[1] || host_table[2]) {
+        // host tables into the thread's table buffer, stream-ordered ahead of the
+        // kernels; the order table's ints last, so the displacements stay 8-byte aligned
+        size_t total = 0;
+        for (int k = 0; k < 3; ++k) total += host_table[k] ? tbytes[k] : 0;
+        char *buf = nullptr;
+        rc = get_tables(dev, total, &buf);
+        if (rc != MPIR_HIP_OK) return rc;               // (nothing of this call is queued yet)
+        for (int k = 0; k < 3; ++k) {
+            if (!host_table[k]) continue;
+            const hipError_t ce = hipMemcpyAsync(buf, table[k], tbytes[k], hipMemcpyHostToDevice, s);
+            if (ce != hipSuccess) {
+                // (another table's copy may be queued on the library stream)
+                ctx().dev[dev].main_pending = true;
+                return set_err(ce, "ordered indexed table copy");
+            }
+            table[k] = buf;
+            buf += tbytes[k];
+        }
+    }
+    hipError_t e = hipSuccess;
+    const ordered_fn launch = g_ordered[op][elem].launch;
+    ordered_launches(p, inbuf, static_cast<const int64_t *>(table[0]), inoutbuf, static_cast<const int64_t *>(table[1]),
+                     static_cast<const int *>(table[2]), disp_unit, nblocks, blocklen,
+                     [&](const OrderedArgs &a, uint64_t groups) {
+                         e = launch(&a, groups, s);
+                         return e == hipSuccess;
+                     });
+    // (launches made before one that failed are still queued on the library stream)
+    if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
+    if (e != hipSuccess) rc = set_err(e, "ordered indexed launch");
+    else if (sync) rc = wait_stream(dev, s);
+    return rc;
+}
+
+int MPIR_Hip_order_worksize(uint64_t nblocks, uint64_t *work_bytes) {
+    if (nblocks > (uint64_t)INT32_MAX) return MPIR_HIP_EARG;
+    *work_bytes = (uint64_t)order_worksize(nblocks);
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_order_build(const int64_t *displs, uint64_t nblocks, int *order, void *work, uint64_t work_bytes,
+                         void *hip_stream, int sync) {
+    if (nblocks > (uint64_t)INT32_MAX) return MPIR_HIP_EARG;
+    if (!nblocks) return MPIR_HIP_OK;
+    ctx().err[0] = 0;
+    const size_t need = order_worksize(nblocks);
+    if (work && work_bytes < need) return MPIR_HIP_EARG;
+    const size_t dbytes = (size_t)nblocks * sizeof(int64_t), obytes = (size_t)nblocks * sizeof(int);
+    int dev = -1, rc = MPIR_HIP_OK;
+    const bool displs_dev = table_on_device(displs, dbytes, &dev, &rc);
+    if (rc != MPIR_HIP_OK) return rc;
+    const bool order_dev = table_on_device(order, obytes, &dev, &rc);
+    if (rc != MPIR_HIP_OK) return rc;
+    if ((!displs_dev || !order_dev) && (hip_stream || !sync)) return MPIR_HIP_EBUFFER;      // a host table with a stream
+    if (!work && hip_stream) return MPIR_HIP_EBUFFER;
+    if (!displs_dev && !order_dev) {
+        // both tables on the host: a host sort, no GPU runtime needed
+        for (uint64_t k = 0; k < nblocks; ++k) order[k] = (int)k;
+        std::stable_sort(order, order + nblocks, [displs](int a, int b) { return displs[a] < displs[b]; });
+        return MPIR_HIP_OK;
+    }
+    if (work) {
+        int wrc = MPIR_HIP_OK;
+        if (!table_on_device(work, need, &dev, &wrc) || wrc != MPIR_HIP_OK) return MPIR_HIP_EBUFFER;
+    }
+    DeviceScope on(dev);
+    if (!on.ok()) return on.err();
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!s) rc = get_stream(dev, S_MAIN, &s);
+    if (rc != MPIR_HIP_OK) return rc;
+    // what the caller did not give in device memory comes from the thread's table
+    // buffer (a synchronous call: done with it on return): a host side's device
+    // copy, and the scratch
+    const size_t al = 256;
+    const size_t part[3] = {displs_dev ? 0 : (dbytes + al - 1) & ~(al - 1), order_dev ? 0 : (obytes + al - 1) & ~(al - 1),
+                            work ? 0 : need};
+    const int64_t *d_displs = displs;
+    int *d_order = order;
+    if (part[0] + part[1] + part[2]) {
+        char *buf = nullptr;
+        rc = get_tables(dev, part[0] + part[1] + part[2], &buf);
+        if (rc != MPIR_HIP_OK) return rc;
+        if (part[0]) {
+            const hipError_t ce = hipMemcpyAsync(buf, displs, dbytes, hipMemcpyHostToDevice, s);
+            if (ce != hipSuccess) {
+                ctx().dev[dev].main_pending = true;
+                return set_err(ce, "order build table copy");
+            }
+            d_displs = reinterpret_cast<const int64_t *>(buf);
+        }
+        if (part[1]) d_order = reinterpret_cast<int *>(buf + part[0]);
+        if (part[2]) {
+            work = buf + part[0] + part[1];
+            work_bytes = need;
+        }
+    }
+    size_t wants = 0;
+    // (never past the reported size, whatever the caller's buffer holds beyond it)
+    work_bytes = need;
+    hipError_t e = order_sort(d_displs, nblocks, d_order, work, need, s, &wants);
+    if (e == hipSuccess && part[1]) e = hipMemcpyAsync(order, d_order, obytes, hipMemcpyDeviceToHost, s);
+    if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
+    if (e != hipSuccess) {
+        if (wants > work_bytes) {
+            snprintf(ctx().err, sizeof(ctx().err), "the order sort needs %zu bytes of work, MPIR_Hip_order_worksize gave %zu",
+                     wants, need);
+            return MPIR_HIP_ERUNTIME;
+        }
+        return set_err(e, "order build");
+    }
+    if (sync) rc = wait_stream(dev, s);
     return rc;
 }
 

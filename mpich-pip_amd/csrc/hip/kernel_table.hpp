@@ -36,6 +36,7 @@ typedef uint64_t (*bgroups_fn)(const void *, const void *, uint64_t, int *);
 typedef hipError_t (*strided_fn)(const StridedArgs *, uint64_t, hipStream_t);
 typedef hipError_t (*fetch_fn)(const FetchArgs *, hipStream_t);
 typedef hipError_t (*indexed_fn)(const IndexedArgs *, uint64_t, hipStream_t);
+typedef hipError_t (*ordered_fn)(const OrderedArgs *, uint64_t, hipStream_t);
 typedef hipError_t (*ragged_fn)(const RaggedArgs *, hipStream_t);
 typedef void (*fplan_fn)(const FetchArgs *, FetchPlan *);
 typedef hipError_t (*fetch_ragged_fn)(const FetchRaggedArgs *, hipStream_t);
@@ -69,6 +70,11 @@ struct FetchEntry { fetch_fn launch; fplan_fn plan; };
 // k_reduce_indexed over a range of blocks (MPIR_Hip_reduce_indexed), for the
 // pairs g_batch holds (reg_indexed<>, from the reg_indexed_*.hip units).
 struct IndexedEntry { indexed_fn launch; };
+// g_ordered[op][elem], likewise: launch_indexed_ordered<Op, T>, one launch of
+// k_reduce_indexed_ordered over a range of sorted positions
+// (MPIR_Hip_reduce_indexed_ordered), for the pairs g_indexed holds
+// (reg_ordered<>, from the reg_ordered_*.hip units).
+struct OrderedEntry { ordered_fn launch; };
 // g_ragged[op][elem], likewise: launch_ragged<Op, T>, the one launch of
 // k_reduce_ragged (MPIR_Hip_reduce_ragged), for the pairs g_indexed holds
 // (reg_ragged<>, from the reg_ragged_*.hip units).
@@ -152,6 +158,7 @@ extern BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern OrderedEntry g_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern RaggedEntry g_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchRaggedEntry g_fetch_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchRaggedEntry g_fetch_ragged_bytes[2][kFetchRaggedSizes];
@@ -193,6 +200,11 @@ void reg_fetch(int op, int elem) {
 template <class Op, class T>
 void reg_indexed(int op, int elem) {
     g_indexed[op][elem] = IndexedEntry{&launch_indexed<Op, T>};
+}
+// the ordered indexed kernel of the same pairs, from the reg_ordered_*.hip units
+template <class Op, class T>
+void reg_ordered(int op, int elem) {
+    g_ordered[op][elem] = OrderedEntry{&launch_indexed_ordered<Op, T>};
 }
 // the ragged kernel of the same pairs, from the reg_ragged_*.hip units
 template <class Op, class T>

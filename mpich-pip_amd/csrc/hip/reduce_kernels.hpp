@@ -1091,6 +1091,315 @@ hipError_t launch_indexed(const IndexedArgs *a, uint64_t groups, hipStream_t s) 
 }
 
 // ============================================================================
+// Ordered indexed reductions (MPIR_Hip_reduce_indexed_ordered): the indexed
+// call with an output table that may name one target block any number of times,
+// the blocks of one target combined one after another in table order -- what a
+// sequence of MPI_Reduce_local calls leaves, bit for bit, and what a target that
+// has queued several accumulates to one location must do.  A third table,
+// `order` (nblocks ints, a stable argsort of io_displs), puts the blocks of one
+// target side by side: a RUN of sorted positions.  Rows of the indexed kernel
+// become sorted positions p; the plan and the forms are the indexed call's.
+//
+//   * Head test: position p heads a run iff p == 0 or io_displs[order[p - 1]]
+//     != io_displs[order[p]].  Only a head works: a workgroup (WIDE) or a lane's
+//     unit (NARROW) at any other position ends at once, having loaded two
+//     entries of each table and no data.
+//   * Run loop: the head loads its tile, vector or element of the target ONCE,
+//     then for q = p, p + 1, ... while q < nblocks and io_displs[order[q]] is
+//     the head's, loads the same piece of input block order[q] and combines it
+//     into registers, each step rounded as the type rounds it; then it stores
+//     once.  A run is folded serially by one slice of one workgroup: the order
+//     is the contract, a tree would change floating-point results.  A target
+//     with very many contributions (a hot row) therefore costs one dependent
+//     chain of table and data loads per contribution.
+//   * Launches: the kernel takes the call's tables and bases unadvanced, the
+//     launch's first sorted position (pos0) and the whole nblocks, so a later
+//     launch's head test looks back across the launch boundary and a run goes on
+//     past its launch's last position.  A run belongs entirely to its head, so no
+//     two workgroups, of one launch or of two, ever write one target.
+//   * WIDE: the split of a target block into workgroups comes from the target's
+//     address alone (seg_split with inoutbuf on both sides: the 16 KiB tile grid
+//     of its address where it is naturally aligned, else the element form), so
+//     that a workgroup owns one piece of the target over the whole run whatever
+//     the input blocks' alignments.  An input block that shares the target's
+//     offset mod 16 is read through a buffer descriptor as reduce_tile reads it;
+//     any other is read element by element into the same registers.  The block
+//     numbers and displacements pass through readfirstlane (wave_uniform64), so
+//     descriptors stay in scalar registers.  G is the indexed call's.
+//   * NARROW_VEC: a lane's four units' order and displacement loads issue in
+//     straight runs, as in the indexed kernel; only heads load data.  A head
+//     then walks its run kOrderedAhead positions at a time: the table entries
+//     of the next four positions load together, then the data of those still
+//     in the run, and the combines follow in order -- three dependent round
+//     trips per four contributions instead of per one.
+//   * Every index read from `order` is clamped into [0, nblocks): a device order
+//     table that breaks its conditions gives an undefined result, but the
+//     kernel's reads of all three tables stay inside them.
+//
+// No LDS, no scratch, no gridDim.  Tile and vector stores are nt.
+// ============================================================================
+struct OrderedArgs {
+    const char *in;             // the call's bases and tables, the same in every launch
+    char *io;
+    const int64_t *in_displs;   // null: packed input, block k at k * the block's bytes
+    const int64_t *io_displs;   // never null
+    const int *order;           // sorted position -> block number
+    uint64_t disp_unit;         // bytes per displacement unit, > 0
+    uint64_t blocklen;          // elements per block, > 0
+    uint32_t nblocks;           // blocks of the whole call
+    uint32_t pos0;              // this launch's first sorted position
+    uint32_t nrows;             // sorted positions of this launch, > 0
+    uint32_t form;              // MPIR_HIP_INDEXED_WIDE / _NARROW_VEC / _NARROW_ELEMS
+    uint32_t per;               // WIDE: G, workgroups per block; NARROW: units per block
+    uint32_t pad_;
+};
+
+// the block at sorted position p (p < nblocks), clamped into the tables
+__device__ __forceinline__ uint32_t ordered_block(const OrderedArgs &a, uint32_t p) {
+    const uint32_t k = (uint32_t)a.order[p];
+    return k < a.nblocks ? k : a.nblocks - 1;
+}
+
+// Element i of the run headed by position p (block k0, displacement d0, target
+// block at io): loaded once, every block of the run combined in, stored once.
+template <class Op, class T>
+__device__ __forceinline__ void ordered_elem_run(const OrderedArgs &a, uint32_t p, uint32_t k0, int64_t d0, char *io,
+                                                 uint64_t row_bytes, uint64_t i) {
+    Op op;
+    T x, y;
+    __builtin_memcpy(&x, io + i * sizeof(T), sizeof(T));
+    uint32_t k = k0;
+    for (uint32_t q = p;;) {
+        const char *in = a.in + indexed_off(a.in_displs, k, a.disp_unit, row_bytes);
+        __builtin_memcpy(&y, in + i * sizeof(T), sizeof(T));
+        x = op(x, y);
+        if (++q >= a.nblocks) break;
+        k = ordered_block(a, q);
+        if (a.io_displs[k] != d0) break;
+    }
+    __builtin_memcpy(io + i * sizeof(T), &x, sizeof(T));
+}
+
+template <class Op, class T>
+__device__ __forceinline__ void reduce_ordered_wide(const OrderedArgs &a) {
+    const uint32_t r = blockIdx.x / a.per;
+    if (r >= a.nrows) return;
+    const uint32_t p = a.pos0 + r;
+    const uint64_t tile = blockIdx.x - r * a.per;
+    const uint64_t row_bytes = a.blocklen * sizeof(T);
+    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ordered_block(a, p));
+    const int64_t d0 = (int64_t)wave_uniform64((uint64_t)a.io_displs[k0]);
+    if (p && a.io_displs[ordered_block(a, p - 1)] == d0) return;           // not a head
+    char *io = a.io + (uint64_t)d0 * a.disp_unit;
+    // the target's own split: an input block's alignment decides only how it is read
+    const SegSplit s = seg_split<T>(io, io, a.blocklen);
+    if (tile >= batch_seg_groups<T>(s, io, a.blocklen)) return;
+    if constexpr (sizeof(T) <= 16) {
+        if (s.tile) {
+            char *iov = io + s.head_bytes;
+            const int64_t start = (int64_t)(tile * kTileBytes) - (int64_t)tile_shift(iov);
+            const uint64_t lo = start > 0 ? (uint64_t)start : 0;
+            if (lo < s.vbytes) {
+                const uint64_t end = (uint64_t)(start + kTileBytes);
+                const int nrec = (int)((end < s.vbytes ? end : s.vbytes) - lo);
+                const int cut = (int)(lo - start);
+                __amdgpu_buffer_rsrc_t rio = __builtin_amdgcn_make_buffer_rsrc((void *)(iov + lo), 0, nrec, 0x00020000);
+                const int t = (int)threadIdx.x;
+                const int wb = (t >> 6) * (kVecPerLane * 1024) + (t & 63) * 16 - cut;
+                u32x4 x[kVecPerLane];
+#pragma unroll
+                for (int u = 0; u < kVecPerLane; ++u)
+                    x[u] = __builtin_amdgcn_raw_buffer_load_b128(rio, wb + u * 1024, 0, kCachePolicyNT);
+                uint32_t k = k0;
+                for (uint32_t q = p;;) {
+                    const uint64_t oi = wave_uniform64(indexed_off(a.in_displs, k, a.disp_unit, row_bytes));
+                    const char *in = a.in + oi + s.head_bytes + lo;
+                    if (((reinterpret_cast<uintptr_t>(in) ^ reinterpret_cast<uintptr_t>(iov + lo)) & 15) == 0) {
+                        __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)in, 0, nrec, 0x00020000);
+                        u32x4 y[kVecPerLane];
+#pragma unroll
+                        for (int u = 0; u < kVecPerLane; ++u)
+                            y[u] = __builtin_amdgcn_raw_buffer_load_b128(rin, wb + u * 1024, 0, kCachePolicyNT);
+#pragma unroll
+                        for (int u = 0; u < kVecPerLane; ++u) x[u] = combine16<Op, T>(x[u], y[u]);
+                    } else {
+                        // an input block off the target's 16-byte phase: its elements one
+                        // by one, only where the lane's vector lies inside the tile
+#pragma unroll
+                        for (int u = 0; u < kVecPerLane; ++u) {
+                            const int off = wb + u * 1024;
+                            if ((unsigned)off < (unsigned)nrec) {
+                                Pack16<T> y;
+#pragma unroll
+                                for (int e = 0; e < (int)(16 / sizeof(T)); ++e)
+                                    __builtin_memcpy(&y.e[e], in + off + e * (int)sizeof(T), sizeof(T));
+                                x[u] = combine16<Op, T>(x[u], __builtin_bit_cast(u32x4, y));
+                            }
+                        }
+                    }
+                    if (++q >= a.nblocks) break;
+                    k = (uint32_t)__builtin_amdgcn_readfirstlane((int)ordered_block(a, q));
+                    if (a.io_displs[k] != d0) break;
+                }
+#pragma unroll
+                for (int u = 0; u < kVecPerLane; ++u) store16(x[u], rio, wb + u * 1024, false);
+            }
+            if (tile == 0) {
+                // the head and tail elements, a lane each as in reduce_seg
+                const unsigned t = threadIdx.x;
+                if (t < s.nhead) ordered_elem_run<Op, T>(a, p, k0, d0, io, row_bytes, t);
+                else if (t >= 64 && t - 64 < s.ntail)
+                    ordered_elem_run<Op, T>(a, p, k0, d0, io, row_bytes, (s.head_bytes + s.vbytes) / sizeof(T) + (t - 64));
+            }
+            return;
+        }
+    }
+    constexpr uint64_t per = kTileBytes / sizeof(T);
+    const uint64_t base = tile * per;
+    const uint64_t end = base + per < a.blocklen ? base + per : a.blocklen;
+    for (uint64_t i = base + threadIdx.x; i < end; i += kThreads) ordered_elem_run<Op, T>(a, p, k0, d0, io, row_bytes, i);
+}
+
+// sorted positions the narrow vector form looks ahead of a run's current end
+constexpr int kOrderedAhead = 4;
+
+template <class Op, class T>
+__device__ __forceinline__ void reduce_ordered_narrow(const OrderedArgs &a) {
+    const uint32_t upr = a.per;                             // units per block
+    const uint64_t row_bytes = a.blocklen * sizeof(T);
+    const unsigned t = threadIdx.x;
+    if constexpr (sizeof(T) <= 16) {
+        if (a.form == MPIR_HIP_INDEXED_NARROW_VEC) {
+            constexpr uint32_t upw = strided_units_per_group<T>(true);
+            constexpr int per_lane = (int)(upw / kThreads);
+            const uint64_t u0 = (uint64_t)blockIdx.x * upw;
+            const uint64_t row0 = u0 / upr;
+            const uint32_t col0 = (uint32_t)(u0 - row0 * upr);
+            // a unit past the launch's last position is clamped into it, as the
+            // indexed kernel clamps: its table loads need no branch
+            const uint64_t last = a.nrows - 1;
+            uint32_t pos[per_lane], k[per_lane], kp[per_lane], kn[per_lane];
+            uint64_t off[per_lane], oi[per_lane];
+            int64_t d[per_lane], dp[per_lane], dn[per_lane];
+            bool head[per_lane];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                const uint32_t c = col0 + t + (uint32_t)j * kThreads;
+                const uint32_t q = c / upr;
+                const uint64_t r = row0 + q;
+                head[j] = r <= last;
+                pos[j] = a.pos0 + (uint32_t)(head[j] ? r : last);
+                off[j] = (uint64_t)(c - q * upr) * 16;
+            }
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) k[j] = ordered_block(a, pos[j]);
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) kp[j] = ordered_block(a, pos[j] ? pos[j] - 1 : 0);
+            // (the position after, with the same loads: whether a run goes on at all is
+            // then known without another round trip, and a run of one ends here)
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) kn[j] = ordered_block(a, pos[j] + 1 < a.nblocks ? pos[j] + 1 : pos[j]);
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) d[j] = a.io_displs[k[j]];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) dp[j] = a.io_displs[kp[j]];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) dn[j] = a.io_displs[kn[j]];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                head[j] = head[j] && (pos[j] == 0 || d[j] != dp[j]);
+                oi[j] = (uint64_t)k[j] * row_bytes;         // the packed place
+            }
+            if (a.in_displs) {
+                int64_t di[per_lane];
+#pragma unroll
+                for (int j = 0; j < per_lane; ++j) di[j] = a.in_displs[k[j]];
+#pragma unroll
+                for (int j = 0; j < per_lane; ++j) oi[j] = (uint64_t)di[j] * a.disp_unit;
+            }
+            // only heads touch data: the target's vector once, its own block's first
+            u32x4 x[per_lane], y[per_lane];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                x[j] = y[j] = u32x4{0, 0, 0, 0};
+                if (head[j]) {
+                    x[j] = __builtin_nontemporal_load((const global_u32x4 *)(a.io + (uint64_t)d[j] * a.disp_unit + off[j]));
+                    y[j] = __builtin_nontemporal_load((const global_u32x4 *)(a.in + oi[j] + off[j]));
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                if (!head[j]) continue;
+                u32x4 v = combine16<Op, T>(x[j], y[j]);
+                // the rest of the run, kOrderedAhead positions at a time: their order
+                // entries, then their displacements, then the data of those that still
+                // belong to the run issue together (a position past the table is
+                // clamped into it and not counted), so a step costs a fraction of the
+                // three dependent round trips; the combines stay in order
+                bool more = dn[j] == d[j];
+                for (uint32_t q = pos[j] + 1; more && q < a.nblocks; q += kOrderedAhead) {
+                    uint32_t kq[kOrderedAhead];
+                    int64_t dq[kOrderedAhead];
+                    uint64_t oq[kOrderedAhead];
+                    u32x4 w[kOrderedAhead];
+                    bool in_run[kOrderedAhead];
+#pragma unroll
+                    for (int i = 0; i < kOrderedAhead; ++i)
+                        kq[i] = ordered_block(a, q + i < a.nblocks ? q + i : a.nblocks - 1);
+#pragma unroll
+                    for (int i = 0; i < kOrderedAhead; ++i) dq[i] = a.io_displs[kq[i]];
+#pragma unroll
+                    for (int i = 0; i < kOrderedAhead; ++i) oq[i] = indexed_off(a.in_displs, kq[i], a.disp_unit, row_bytes);
+#pragma unroll
+                    for (int i = 0; i < kOrderedAhead; ++i) {
+                        more = more && q + i < a.nblocks && dq[i] == d[j];
+                        w[i] = u32x4{0, 0, 0, 0};
+                        if (more) w[i] = __builtin_nontemporal_load((const global_u32x4 *)(a.in + oq[i] + off[j]));
+                        in_run[i] = more;
+                    }
+#pragma unroll
+                    for (int i = 0; i < kOrderedAhead; ++i)
+                        if (in_run[i]) v = combine16<Op, T>(v, w[i]);
+                }
+                __builtin_nontemporal_store(v, (global_u32x4 *)(a.io + (uint64_t)d[j] * a.disp_unit + off[j]));
+            }
+            return;
+        }
+    }
+    constexpr uint32_t upw = strided_units_per_group<T>(false);
+    const uint64_t u0 = (uint64_t)blockIdx.x * upw;
+    const uint64_t row0 = u0 / upr;
+    const uint32_t col0 = (uint32_t)(u0 - row0 * upr);
+    for (uint32_t u = t; u < upw; u += kThreads) {
+        const uint32_t c = col0 + u;
+        const uint32_t q = c / upr;
+        const uint64_t r = row0 + q;
+        if (r >= a.nrows) break;                            // positions only grow with u
+        const uint32_t p = a.pos0 + (uint32_t)r;
+        const uint32_t k0 = ordered_block(a, p);
+        const int64_t d0 = a.io_displs[k0];
+        if (p && a.io_displs[ordered_block(a, p - 1)] == d0) continue;      // not a head
+        ordered_elem_run<Op, T>(a, p, k0, d0, a.io + (uint64_t)d0 * a.disp_unit, row_bytes, c - q * upr);
+    }
+}
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_reduce_indexed_ordered(OrderedArgs a) {
+    if (a.form == MPIR_HIP_INDEXED_WIDE) reduce_ordered_wide<Op, T>(a);
+    else reduce_ordered_narrow<Op, T>(a);
+}
+
+// one launch: `groups` workgroups over sorted positions [pos0, pos0 + nrows)
+template <class Op, class T>
+hipError_t launch_indexed_ordered(const OrderedArgs *a, uint64_t groups, hipStream_t s) {
+    if (!a->nrows || !a->per || !a->blocklen || !a->disp_unit || !a->io_displs || !a->order ||
+        (uint64_t)a->pos0 + a->nrows > a->nblocks || groups < 1 || groups > kBatchMaxGroups)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_reduce_indexed_ordered<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+// ============================================================================
 // Ragged reductions (MPIR_Hip_reduce_ragged): npieces unequal pieces, piece k of
 // starts[k + 1] - starts[k] elements (starts: npieces + 1 packed element offsets,
 // CSR row pointers, a device table) at in + in_displs[k] * disp_unit and io +

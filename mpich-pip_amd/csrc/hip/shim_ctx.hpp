@@ -29,6 +29,11 @@ uint32_t direct_test_write_delay_us(uint32_t us);
 void direct_test_fail_probe();
 void direct_placement(int dev, int out[5]);
 
+// order_build.hip (the sort of MPIR_Hip_order_build: see there)
+size_t order_worksize(uint64_t n);
+hipError_t order_sort(const int64_t *displs, uint64_t n, int *order, void *work, size_t work_bytes, hipStream_t s,
+                      size_t *need);
+
 // ------------------------------------------------------------ per-thread state
 constexpr int kMaxDev = 64;
 constexpr int kMaxStageSlots = 8;
@@ -212,7 +217,9 @@ inline int get_zc(int dev, size_t bytes, char **out) {
 
 // the calling thread's table buffer on `dev`: one call's host tables side by
 // side in `bytes` (MPIR_Hip_reduce_indexed's two displacement tables,
-// MPIR_Hip_reduce_ragged's two and its starts).  Not `scratch`: stream-variant work may still be reading that,
+// MPIR_Hip_reduce_ragged's two and its starts, MPIR_Hip_reduce_indexed_ordered's
+// two and its order; a synchronous MPIR_Hip_order_build's host side and, where
+// the caller gave none, its work).  Not `scratch`: stream-variant work may still be reading that,
 // while this buffer's only readers are synchronous calls, complete when they
 // returned -- but for one that failed after it enqueued, hence the wait.
 inline int get_tables(int dev, size_t bytes, char **out) {

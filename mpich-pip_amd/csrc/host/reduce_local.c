@@ -749,6 +749,170 @@ static int reduce_local_indexed(const void *inbuf, const MPI_Aint * in_displs, v
     return MPI_SUCCESS;
 }
 
+/* ---- MPIX_Reduce_local_indexed_ordered: repeated targets in table order (see the header) */
+/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
+#pragma weak MPIR_Hip_reduce_indexed_ordered
+#pragma weak MPIR_Hip_order_build
+#pragma weak MPIR_Hip_order_worksize
+static int reduce_local_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                                        const MPI_Aint * inout_displs, const int *order, MPI_Aint disp_unit,
+                                        int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op,
+                                        void *hip_stream);
+static int reduce_local_order(const MPI_Aint * displs, int nblocks, int *order, void *work, MPI_Aint work_bytes,
+                              void *hip_stream);
+
+int MPIX_Reduce_local_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                                      const MPI_Aint * inout_displs, const int *order, MPI_Aint disp_unit,
+                                      int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    int rc;
+    /* no order table: the indexed call unchanged, its own name on the error stack */
+    if (order == NULL)
+        return MPIX_Reduce_local_indexed(inbuf, in_displs, inoutbuf, inout_displs, disp_unit, nblocks, blocklen,
+                                         datatype, op, hip_stream);
+    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
+    rc = reduce_local_indexed_ordered(inbuf, in_displs, inoutbuf, inout_displs, order, disp_unit, nblocks, blocklen,
+                                      datatype, op, hip_stream);
+    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
+    return rc;
+}
+
+static int reduce_local_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                                        const MPI_Aint * inout_displs, const int *order, MPI_Aint disp_unit,
+                                        int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op,
+                                        void *hip_stream)
+{
+    static const char *fc = "MPIX_Reduce_local_indexed_ordered";
+    int mpi_errno, opidx, elem, rc;
+    const int empty = nblocks == 0 || blocklen == 0;
+    if (nblocks < 0 || blocklen < 0) {
+        MPIR_Err_set_detail("negative %s %d", nblocks < 0 ? "nblocks" : "blocklen", nblocks < 0 ? nblocks : blocklen);
+        return err_return(fc, MPI_ERR_COUNT);
+    }
+    /* the indexed call's order: an empty call's pointers are not looked at (the
+     * op still is) */
+    mpi_errno = empty ? validate(NULL, NULL, 0, datatype, op) : validate(inbuf, inoutbuf, blocklen, datatype, op);
+    if (mpi_errno != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
+    if (disp_unit <= 0) {
+        MPIR_Err_set_detail("disp_unit %ld is not positive", (long) disp_unit);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (empty)
+        return MPI_SUCCESS;
+    if (inout_displs == NULL) {
+        MPIR_Err_set_detail("an order table with no inout_displs: a packed target has no repeats to order");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
+        MPIR_Err_set_detail("user MPI_Op functions run on the host; use MPI_Reduce_local");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    opidx = op & 0xf;
+    elem = MPIR_Op_resolve_elem(opidx, datatype);
+    if (!elem) {        /* compute switch `default:` (LAND/LOR on floats) */
+        MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
+        return err_return(fc, MPI_ERR_OP);
+    }
+    if (!MPIR_Hip_reduce_indexed_ordered) {
+        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_indexed_ordered");
+        return err_return(fc, MPI_ERR_OTHER);
+    }
+    rc = MPIR_Hip_reduce_indexed_ordered(inbuf, (const int64_t *) in_displs, inoutbuf, (const int64_t *) inout_displs,
+                                         order, (uint64_t) disp_unit, (uint64_t) nblocks, (uint64_t) blocklen, opidx,
+                                         elem, hip_stream, hip_stream == NULL);
+    if (rc == MPIR_HIP_EBUFFER) {
+        MPIR_Err_set_detail("%s needs device-resident operands on one device, and its tables there too "
+                            "(host tables: the synchronous call only)", fc);
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (rc == MPIR_HIP_EARG) {
+        MPIR_Err_set_detail("%s: a block's offset does not fit the address space, or the order table is not "
+                            "a stable sort of inout_displs", fc);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (rc != MPIR_HIP_OK) {
+        MPIR_Op_report_hip_error(fc, rc);
+        return err_return(fc, *MPIR_Op_errno_ptr());
+    }
+    return MPI_SUCCESS;
+}
+
+int MPIX_Reduce_local_order_worksize(int nblocks, MPI_Aint * work_bytes)
+{
+    static const char *fc = "MPIX_Reduce_local_order_worksize";
+    uint64_t bytes = 0;
+    int rc = MPI_SUCCESS;
+    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
+    if (nblocks < 0) {
+        MPIR_Err_set_detail("negative nblocks %d", nblocks);
+        rc = err_return(fc, MPI_ERR_COUNT);
+    } else if (work_bytes == NULL) {
+        MPIR_Err_set_detail("work_bytes is NULL");
+        rc = err_return(fc, MPI_ERR_ARG);
+    } else if (!MPIR_Hip_order_worksize) {
+        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_order_worksize");
+        rc = err_return(fc, MPI_ERR_OTHER);
+    } else {
+        (void) MPIR_Hip_order_worksize((uint64_t) nblocks, &bytes);     /* (an int is always in its range) */
+        *work_bytes = (MPI_Aint) bytes;
+    }
+    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
+    return rc;
+}
+
+int MPIX_Reduce_local_order(const MPI_Aint * displs, int nblocks, int *order, void *work, MPI_Aint work_bytes,
+                            void *hip_stream)
+{
+    int rc;
+    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
+    rc = reduce_local_order(displs, nblocks, order, work, work_bytes, hip_stream);
+    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
+    return rc;
+}
+
+static int reduce_local_order(const MPI_Aint * displs, int nblocks, int *order, void *work, MPI_Aint work_bytes,
+                              void *hip_stream)
+{
+    static const char *fc = "MPIX_Reduce_local_order";
+    int rc;
+    if (nblocks < 0) {
+        MPIR_Err_set_detail("negative nblocks %d", nblocks);
+        return err_return(fc, MPI_ERR_COUNT);
+    }
+    if (nblocks == 0)
+        return MPI_SUCCESS;
+    if (displs == NULL || order == NULL) {
+        MPIR_Err_set_detail("%s is NULL", displs == NULL ? "displs" : "order");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (work != NULL && work_bytes < 0) {
+        MPIR_Err_set_detail("negative work_bytes %ld", (long) work_bytes);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (!MPIR_Hip_order_build) {
+        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_order_build");
+        return err_return(fc, MPI_ERR_OTHER);
+    }
+    rc = MPIR_Hip_order_build((const int64_t *) displs, (uint64_t) nblocks, order, work, (uint64_t) work_bytes,
+                              hip_stream, hip_stream == NULL);
+    if (rc == MPIR_HIP_EBUFFER) {
+        MPIR_Err_set_detail("%s needs its tables and work in device memory on one device (host tables, or no "
+                            "work: the synchronous call only)", fc);
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (rc == MPIR_HIP_EARG) {
+        MPIR_Err_set_detail("%s: work_bytes %ld is less than MPIX_Reduce_local_order_worksize reports", fc,
+                            (long) work_bytes);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (rc != MPIR_HIP_OK) {
+        MPIR_Op_report_hip_error(fc, rc);
+        return err_return(fc, *MPIR_Op_errno_ptr());
+    }
+    return MPI_SUCCESS;
+}
+
 /* ---- MPIX_Reduce_local_ragged: unequal pieces from a table of packed offsets (see the header) */
 /* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
 #pragma weak MPIR_Hip_reduce_ragged

@@ -116,6 +116,8 @@ EXPORTED_SYMBOLS = [
     "MPIR_Hip_set_strided_wide_bytes", "MPIR_Hip_strided_test_max_groups",
     "MPIX_Reduce_local_fetch", "MPIR_Hip_reduce_fetch", "MPIR_Hip_fetch_plan_info",
     "MPIX_Reduce_local_indexed", "MPIR_Hip_reduce_indexed", "MPIR_Hip_indexed_plan_info",
+    "MPIX_Reduce_local_indexed_ordered", "MPIR_Hip_reduce_indexed_ordered", "MPIR_Hip_indexed_ordered_plan_info",
+    "MPIX_Reduce_local_order", "MPIX_Reduce_local_order_worksize", "MPIR_Hip_order_build", "MPIR_Hip_order_worksize",
     "MPIX_Reduce_local_ragged", "MPIR_Hip_reduce_ragged", "MPIR_Hip_ragged_plan_info",
     "MPIX_Reduce_local_fetch_ragged", "MPIR_Hip_reduce_fetch_ragged", "MPIR_Hip_fetch_ragged_plan_info",
     # device collectives (include/mpix_hip_coll.h)
@@ -209,6 +211,20 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.MPIR_Hip_reduce_indexed.restype = i32
     lib.MPIR_Hip_indexed_plan_info.argtypes = [vp, vp, vp, vp, u64, u64, u64, i32, i32, ctypes.POINTER(u64)]
     lib.MPIR_Hip_indexed_plan_info.restype = i32
+    lib.MPIX_Reduce_local_indexed_ordered.argtypes = [vp, vp, vp, vp, vp, ctypes.c_long, i32, i32, i32, i32, vp]
+    lib.MPIX_Reduce_local_indexed_ordered.restype = i32
+    lib.MPIR_Hip_reduce_indexed_ordered.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, vp, i32]
+    lib.MPIR_Hip_reduce_indexed_ordered.restype = i32
+    lib.MPIR_Hip_indexed_ordered_plan_info.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, ctypes.POINTER(u64)]
+    lib.MPIR_Hip_indexed_ordered_plan_info.restype = i32
+    lib.MPIX_Reduce_local_order.argtypes = [vp, i32, vp, vp, ctypes.c_long, vp]
+    lib.MPIX_Reduce_local_order.restype = i32
+    lib.MPIX_Reduce_local_order_worksize.argtypes = [i32, ctypes.POINTER(ctypes.c_long)]
+    lib.MPIX_Reduce_local_order_worksize.restype = i32
+    lib.MPIR_Hip_order_build.argtypes = [vp, u64, vp, vp, u64, vp, i32]
+    lib.MPIR_Hip_order_build.restype = i32
+    lib.MPIR_Hip_order_worksize.argtypes = [u64, ctypes.POINTER(u64)]
+    lib.MPIR_Hip_order_worksize.restype = i32
     lib.MPIX_Reduce_local_ragged.argtypes = [vp, vp, vp, vp, vp, ctypes.c_long, i32, i32, i32, i32, vp]
     lib.MPIX_Reduce_local_ragged.restype = i32
     lib.MPIR_Hip_reduce_ragged.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, vp, i32]
@@ -586,6 +602,66 @@ def indexed_plan_info(inbuf: int, in_displs, inoutbuf: int, inout_displs, disp_u
         raise ValueError("MPIR_Hip_indexed_plan_info: arguments refused")
     if rc:
         raise LookupError(f"MPIR_Hip_indexed_plan_info: {rc}")
+    return dict(zip(("form", "launches", "groups", "per", "threshold", "rows_per_launch"), (int(v) for v in out)))
+
+
+# ---- ordered indexed reductions (MPIX_Reduce_local_indexed_ordered)
+def _order_addr(order) -> int:
+    """An order table's address: None / 0 (no table), a raw address, or a
+    C-contiguous numpy int32 array (a host table; the caller keeps it alive)."""
+    if order is None or isinstance(order, int):
+        return order or 0
+    if str(order.dtype) != "int32" or not order.flags["C_CONTIGUOUS"]:
+        raise TypeError("an order table is a C-contiguous int32 array (int)")
+    return order.ctypes.data
+
+
+def reduce_local_indexed_ordered(inbuf: int, in_displs, inoutbuf: int, inout_displs, order, disp_unit: int,
+                                 nblocks: int, blocklen: int, datatype: int, op: int, stream: int = 0) -> int:
+    """MPIX_Reduce_local_indexed_ordered: reduce_local_indexed whose inout_displs
+    may repeat, the blocks of one target applied in table order.  order: the
+    stable argsort of inout_displs as int32 (a raw address or a numpy array, see
+    _order_addr; reduce_local_order makes one); None: the indexed call."""
+    return load().MPIX_Reduce_local_indexed_ordered(
+        ctypes.c_void_p(inbuf or None), ctypes.c_void_p(_table_addr(in_displs) or None), ctypes.c_void_p(inoutbuf or None),
+        ctypes.c_void_p(_table_addr(inout_displs) or None), ctypes.c_void_p(_order_addr(order) or None), disp_unit,
+        nblocks, blocklen, datatype, op, ctypes.c_void_p(stream or None))
+
+
+def reduce_local_order_worksize(nblocks: int) -> int:
+    """MPIX_Reduce_local_order_worksize: the bytes of scratch reduce_local_order
+    may use for nblocks (no GPU needed).  Raises ValueError where it refuses."""
+    out = ctypes.c_long(0)
+    rc = load().MPIX_Reduce_local_order_worksize(nblocks, ctypes.byref(out))
+    if rc:
+        raise ValueError(f"MPIX_Reduce_local_order_worksize: {error_string(rc)}")
+    return int(out.value)
+
+
+def reduce_local_order(displs, nblocks: int, order, work: int = 0, work_bytes: int = 0, stream: int = 0) -> int:
+    """MPIX_Reduce_local_order: order = the stable argsort of displs[0:nblocks].
+    displs: a raw address or a numpy int64 array; order: a raw address or a numpy
+    int32 array (written); work: a raw device address of work_bytes bytes, or 0
+    (the library's own buffer: the synchronous call only)."""
+    return load().MPIX_Reduce_local_order(ctypes.c_void_p(_table_addr(displs) or None), nblocks,
+                                          ctypes.c_void_p(_order_addr(order) or None), ctypes.c_void_p(work or None),
+                                          work_bytes, ctypes.c_void_p(stream or None))
+
+
+def indexed_ordered_plan_info(inbuf: int, in_displs, inoutbuf: int, inout_displs, order, disp_unit: int, nblocks: int,
+                              blocklen: int, datatype: int, op: int) -> dict:
+    """MPIR_Hip_indexed_ordered_plan_info: indexed_plan_info's outputs for the
+    launches of the ordered call (rows are sorted positions; order is only
+    compared with 0).  Raises as indexed_plan_info does."""
+    out = (ctypes.c_uint64 * 6)()
+    rc = load().MPIR_Hip_indexed_ordered_plan_info(
+        ctypes.c_void_p(inbuf or None), ctypes.c_void_p(_table_addr(in_displs) or None), ctypes.c_void_p(inoutbuf or None),
+        ctypes.c_void_p(_table_addr(inout_displs) or None), ctypes.c_void_p(_order_addr(order) or None), disp_unit,
+        nblocks, blocklen, op & 0xFF, _ELEM_BY_HANDLE[datatype], out)
+    if rc == MPIR_HIP_EARG:
+        raise ValueError("MPIR_Hip_indexed_ordered_plan_info: arguments refused")
+    if rc:
+        raise LookupError(f"MPIR_Hip_indexed_ordered_plan_info: {rc}")
     return dict(zip(("form", "launches", "groups", "per", "threshold", "rows_per_launch"), (int(v) for v in out)))
 
 
