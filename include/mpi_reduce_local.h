@@ -376,7 +376,9 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_fetch(const void *inbuf, void *inoutbuf, 
  *       block, are undefined and not checked: MPI forbids overlapping target
  *       entries in an accumulate, and the blocks run concurrently.  A table with
  *       repeated targets (embedding rows hit twice, several accumulates queued
- *       to one location) is MPIX_Reduce_local_indexed_ordered's.
+ *       to one location) is MPIX_Reduce_local_indexed_ordered's.  The old
+ *       target blocks out as well (a Get_accumulate on this shape) is
+ *       MPIX_Reduce_local_fetch_indexed_ordered with order NULL.
  *   Ops and types as the strided call validates them, in its order: MPI_REPLACE,
  *       MPI_NO_OP, null, invalid and user ops, and MPI_LAND / MPI_LOR on
  *       floating types: MPI_ERR_OP; nblocks < 0 or blocklen < 0: MPI_ERR_COUNT;
@@ -429,7 +431,8 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_indexed(const void *inbuf, const MPI_Aint
  * bit for bit (in_off, io_off: the indexed call's), deterministic where atomics
  * are not; each distinct target block is read once and written once, however
  * many contributions it gets.  No byte outside the blocks is read or written,
- * and no table is written.
+ * and no table is written.  The value the target held before each contribution
+ * (MPI_Fetch_and_op, MPI_Get_accumulate) is MPIX_Reduce_local_fetch_indexed_ordered's.
  *   Two output blocks must have equal inout_displs entries or be disjoint;
  *       partial overlap stays undefined, as does an input block that overlaps
  *       an output block.
@@ -648,7 +651,8 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_ragged(const void *inbuf, const MPI_Aint 
  *   Equal-block and constant-stride targets (MPI_Type_create_indexed_block,
  *       MPI_Type_vector) are expressed with a uniform starts, starts[k] = k x
  *       blocklen; a starts == NULL shortcut for equal pieces is deliberately not
- *       part of this call.
+ *       part of this call.  Equal blocks whose targets repeat, each contribution
+ *       fetching what the one before left, are MPIX_Reduce_local_fetch_indexed_ordered's.
  * Measured (Fetching ragged reductions, has the tables and the spread
  * of the rounds): against what a caller did before, a device copy per piece into
  * fetchbuf followed by MPIX_Reduce_local_ragged, this call takes less time at
@@ -666,6 +670,101 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_fetch_ragged(const void *inbuf, void *ino
                              const MPI_Aint * inout_displs, void *fetchbuf, const MPI_Aint * starts,
                              MPI_Aint disp_unit, int npieces, int count, MPI_Datatype datatype, MPI_Op op,
                              void *hip_stream);
+/* Fetching ordered indexed local reduction: an ordered fetch-and-op.
+ * MPIX_Reduce_local_indexed_ordered with every intermediate value handed out --
+ * what the MPI_Fetch_and_op / MPI_Get_accumulate operations an RMA target has
+ * queued for one location must each answer, the value the target held just
+ * before that operation ("'copy data + ACC' needs to be atomic",
+ * src/mpid/ch3/src/ch3u_rma_pkthandler.c:899-917); also a deterministic
+ * fetch-and-add (slot or ticket allocation, histograms that hand out positions),
+ * an exclusive running reduction per key in table order (a segmented scan by
+ * key), and with MPI_REPLACE a chain of swaps.  The call is exactly
+ *   for k = 0 .. nblocks - 1, one after another in that order:
+ *     MPIX_Reduce_local_fetch((char *) inbuf + in_off(k), (char *) inoutbuf + io_off(k),
+ *                             (char *) fetchbuf + k * blocklen * size, blocklen, datatype, op, ...)
+ * (in_off, io_off: the indexed call's; fetchbuf is packed by block number), in
+ * the ordered call's launches: fetchbuf block k receives the bytes the target
+ * block held after contributions 0 .. k - 1 and before contribution k, and the
+ * target ends as MPIX_Reduce_local_indexed_ordered would leave it.
+ *   One value: what is stored to fetchbuf and what is combined is one and the
+ *       same register value.  The target is loaded once per run of equal
+ *       displacements and stored once per run; for MPI_NO_OP it is never stored.
+ *   The first block of a run is a byte copy of the old target (NaN payloads, x87
+ *       slot padding and pair padding arrive untouched); later blocks of a run
+ *       are the bytes the ordered call would have stored at that step.
+ *   No byte outside the blocks, outside fetchbuf[0, nblocks x blocklen x size),
+ *       or in any table is written.
+ *   Ops: validated as MPIX_Reduce_local_fetch validates them
+ *       (MPIR_ERRTEST_OP_GACC plus MPI_Reduce_local's datatype check; user ops,
+ *       and MPI_LAND / MPI_LOR on floating types: MPI_ERR_OP).  MPI_NO_OP and
+ *       MPI_REPLACE are accepted on every basic type, both kernels here, byte
+ *       operations chosen by the element's size.  MPI_NO_OP makes every block of
+ *       a run receive the same old bytes; inbuf and in_displs are not looked at
+ *       and may be NULL; the target is not written.  MPI_REPLACE gives fetchbuf
+ *       block k the previous contribution's block (the head of a run: the old
+ *       target), and the target ends holding the run's last input block.
+ *   order given: the ordered call's table under its rules, from
+ *       MPIX_Reduce_local_order unchanged.  order NULL with inout_displs given:
+ *       the positions are the table's own -- the caller's promise that equal
+ *       entries of inout_displs, if any, are adjacent in the table; in
+ *       particular that there are none, which makes this the fetching indexed
+ *       call, a Get_accumulate on an indexed_block target, with no sort.  A host
+ *       inout_displs is held to the promise: an entry equal to a non-adjacent
+ *       earlier one is MPI_ERR_ARG.  inout_displs NULL with order given is
+ *       MPI_ERR_ARG, as in the ordered call; with in_displs given too: a packed
+ *       target has no repeats, and a gather on the origin side is not this
+ *       call's job.  Both NULL is MPIX_Reduce_local_fetch on nblocks x blocklen
+ *       elements.
+ *   Arguments: the ordered call's checks in its order, the fetch call's op rule
+ *       in the op's place.  After the alias check (inbuf == inoutbuf, unless
+ *       MPI_NO_OP) the fetch call's rules for fetchbuf: MPI_IN_PLACE for any of
+ *       the three buffers is MPI_ERR_BUFFER; fetchbuf NULL with both counts
+ *       positive is MPI_ERR_BUFFER; its range overlapping a packed inbuf's range
+ *       (in_displs NULL) is MPI_ERR_BUFFER whatever the alias check says, unless
+ *       the op is MPI_NO_OP.  Either count 0 succeeds and looks at no pointer or
+ *       table; the op and disp_unit are still checked.
+ *   Bases and tables have the ordered call's residency rules: device memory on
+ *       one device, or, with hip_stream NULL, a table in host memory, which gets
+ *       the ordered call's checks; with a stream a host table is MPI_ERR_BUFFER.
+ *       With a host inout_displs, fetchbuf meeting ANY byte from the lowest
+ *       block's first to the highest block's last is MPI_ERR_BUFFER (the
+ *       fetching ragged call's rule); with device tables those overlaps are
+ *       undefined.  Every index read from a device order stays clamped, so the
+ *       stores to fetchbuf stay inside it too.
+ *   A call that returns an error has written nothing.
+ *   With device tables everything travels in the kernel arguments: no
+ *       allocation and no library scratch, so the call can be captured into a
+ *       graph.
+ *   Blocks below the wide threshold move as 16-byte vectors under the indexed
+ *       call's conditions with fetchbuf a multiple of 16 as well; else element
+ *       by element.  A run is folded serially, as in the ordered call: a hot
+ *       row costs time in proportion to its contributions.
+ *   Measured: fp32 MPI_SUM, synchronous calls, medians of alternated rounds, the
+ *       rounds' medians within 1 % of these but where noted
+ *       (tools/fetch_ordered_ab.py, profiles/fetch_ordered/fetch_ordered_ab.log;
+ *       DESIGN.md, Fetching ordered indexed reductions, has the table).  Against
+ *       MPIX_Reduce_local_indexed_ordered on the same operands, the cost of the
+ *       extra store stream: 65,536 blocks of 256 bytes 27.0 against 22.6 us with
+ *       no repeats (1.19 x), 47.5 against 35.6 at 4 blocks per target (1.34 x),
+ *       65.7 against 52.0 at 64 (1.26 x); 4096 blocks of 64 KiB 178 against 143
+ *       us (1.25 x; 177 to 184 between rounds), 127 against 96 (1.32 x), 499
+ *       against 340 (1.47 x) -- below what the bytes alone would make it (1.33,
+ *       1.67 and 1.97 x).  Against what a caller had before, one
+ *       MPIX_Reduce_local_fetch_ragged per duplicate-free round (the split and
+ *       the packing of each round not timed): at 4 per target 47.5 against 66.5
+ *       us and 127 against 234, at 64 per target 65.7 against 925 and 499
+ *       against 1036.  With NO repeats that way is a single fetch_ragged call
+ *       and takes LESS time than this call with an order table on 256-byte
+ *       blocks, 24.5 against 27.0 us (64 KiB blocks: 189 against 178): a table
+ *       known to be free of repeats should pass order NULL, which reads no order
+ *       table and takes 24.0 us (0.97 x fetch_ragged) and 173 us (0.92 x).  A
+ *       hot row, every block on one target: 29.4 ms for 65,536 blocks of 256
+ *       bytes (0.45 us a contribution; 29.0 to 30.3 between rounds), 4.6 ms for
+ *       4096 of 64 KiB (1.1 us), 1.04 and 1.09 x the ordered call. */
+MPICH_API_PUBLIC int MPIX_Reduce_local_fetch_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs,
+                             void *inoutbuf, const MPI_Aint * inout_displs, void *fetchbuf, const int *order,
+                             MPI_Aint disp_unit, int nblocks, int blocklen,
+                             MPI_Datatype datatype, MPI_Op op, void *hip_stream);
 MPICH_API_PUBLIC int MPIX_Reduce_local_set_errhandler(MPI_Errhandler errhandler);
 MPICH_API_PUBLIC int MPIX_Reduce_local_get_errhandler(MPI_Errhandler * errhandler);
 

@@ -214,7 +214,7 @@ uint64_t MPIR_Hip_strided_test_max_groups(uint64_t groups);
  * undefined here (MPIX_Reduce_local_fetch refuses it).  hip_stream / sync as for
  * MPIR_Hip_reduce; the launch carries everything in its kernel arguments.
  * MPIR_HIP_ENOKERNEL for pairs with no kernel. */
-#define MPIR_HIP_OP_NO_OP 14   /* MPI_NO_OP's table index; MPIR_Hip_reduce_fetch and MPIR_Hip_reduce_fetch_ragged alone take it (no kernel table slot) */
+#define MPIR_HIP_OP_NO_OP 14   /* MPI_NO_OP's table index; the fetching calls (MPIR_Hip_reduce_fetch, _fetch_ragged, _fetch_indexed_ordered) alone take it (no kernel table slot) */
 int MPIR_Hip_reduce_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, uint64_t count, int op, int elem,
                           void *hip_stream, int sync);
 
@@ -470,6 +470,68 @@ int MPIR_Hip_reduce_fetch_ragged(const void *inbuf, void *inoutbuf, const int64_
 int MPIR_Hip_fetch_ragged_plan_info(const void *inbuf, const void *inoutbuf, const int64_t *io_displs,
                                     const void *fetchbuf, const int64_t *starts, uint64_t disp_unit, uint64_t npieces,
                                     uint64_t count, int op, int elem, uint64_t out[7]);
+
+/* Fetching ordered indexed reduction: MPIR_Hip_reduce_indexed_ordered with every
+ * intermediate value handed out -- MPIR_Hip_reduce_fetch block by block in table
+ * order.  For k = 0 .. nblocks - 1 in that order, with in_k and io_k the indexed
+ * call's blocks: the blocklen * size bytes of fetchbuf at k * blocklen * size
+ * (fetchbuf is packed by block number) receive the bytes io_k holds after
+ * contributions 0 .. k - 1 and before contribution k, and io_k = op(io_k, in_k).
+ * What each of the MPI_Fetch_and_op / MPI_Get_accumulate operations a target has
+ * queued for one location must answer.  The kernel
+ * (k_reduce_fetch_indexed_ordered, reduce_kernels.hpp) is the ordered kernel's
+ * code storing its running registers before each combine: the value fetched and
+ * the value combined are one, the target is loaded once and stored once per run
+ * of equal displacements.  The first block of a run receives a byte copy of the
+ * old target (never a value of the type); a later one the bytes the ordered call
+ * would have stored had the run ended before it.  The target ends as
+ * MPIR_Hip_reduce_indexed_ordered leaves it.  No byte outside the blocks, outside
+ * fetchbuf's nblocks * blocklen * size, or in any table is written.
+ * op: an MPIR_Hip_op the ordered call has a kernel for, or
+ *   MPIR_HIP_OP_NO_OP    every block of a run receives the old target; inbuf and
+ *                        in_displs are never looked at (they may be NULL), the
+ *                        target is not written;
+ *   MPIR_HIP_OP_REPLACE  fetchbuf block k receives the previous contribution's
+ *                        input block (the head of a run: the old target); the
+ *                        target ends holding the run's last input block;
+ * both byte operations with a kernel per element size, for every element class.
+ * Tables: `order` as for the ordered call (MPIR_Hip_order_build makes it).
+ * order NULL with io_displs given: sorted position p is block p, the caller's
+ * promise that equal entries of io_displs, if any, are adjacent in the table (in
+ * particular: no repeats, the fetching indexed call); a host io_displs is held to
+ * it (an entry equal to a non-adjacent earlier one: MPIR_HIP_EARG).  io_displs
+ * NULL: with order or in_displs given MPIR_HIP_EARG (a packed target has no
+ * repeats, and gathering the origin side is not this call's job), with neither
+ * MPIR_Hip_reduce_fetch on nblocks * blocklen elements.
+ * The argument checks and their order are the ordered call's (disp_unit, counts
+ * of 0 succeed looking at no pointer, nblocks > INT32_MAX), the op looked up as
+ * MPIR_Hip_reduce_fetch_ragged looks it up.  Residency as the ordered call's,
+ * fetchbuf's first and last byte on the same device (else MPIR_HIP_EBUFFER);
+ * host tables in a synchronous call on the library stream only, checked as the
+ * ordered call checks them; and with a host io_displs a fetchbuf range that meets
+ * any byte from the lowest block's first to the highest block's last is
+ * MPIR_HIP_EBUFFER.  With a device io_displs that overlap is undefined, as is
+ * fetchbuf overlapping an input block (MPIX_Reduce_local_fetch_indexed_ordered
+ * refuses a packed inbuf's range).  Every index read from a device order table
+ * is clamped into [0, nblocks), so the stores to fetchbuf stay inside it too.
+ * A call that fails has written nothing.  With device tables everything travels
+ * in the kernel arguments (no allocation, no library buffer: graph-capturable).
+ * The plan is the ordered call's with fetchbuf joining the alignment test:
+ * NARROW_VEC needs fetchbuf at a multiple of 16 as well, else NARROW_ELEMS. */
+int MPIR_Hip_reduce_fetch_indexed_ordered(const void *inbuf, const int64_t *in_displs, void *inoutbuf,
+                                          const int64_t *io_displs, void *fetchbuf, const int *order, uint64_t disp_unit,
+                                          uint64_t nblocks, uint64_t blocklen, int op, int elem, void *hip_stream,
+                                          int sync);
+
+/* For tests and tools: MPIR_Hip_indexed_ordered_plan_info's six outputs for the
+ * launches MPIR_Hip_reduce_fetch_indexed_ordered would make (the tables are only
+ * compared with NULL; for NO_OP inbuf and in_displs are not looked at).  No
+ * table at all (SINGLE) reports MPIR_Hip_fetch_plan_info's launches and grid.
+ * Returns as that call does, residency and the tables' contents apart. */
+int MPIR_Hip_fetch_indexed_ordered_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
+                                             const int64_t *io_displs, const void *fetchbuf, const int *order,
+                                             uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen, int op, int elem,
+                                             uint64_t out[6]);
 
 /* Flags for the calling thread's later MPIR_Hip_combine calls; returns the
  * previous flags.  MPIR_HIP_COMBINE_UNCAPPED: the fused folds run without the

@@ -39,6 +39,8 @@ RaggedEntry g_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchRaggedEntry g_fetch_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchRaggedEntry g_fetch_ragged_bytes[2][kFetchRaggedSizes];
+FetchOrderedEntry g_fetch_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+FetchOrderedEntry g_fetch_ordered_bytes[2][kFetchRaggedSizes];
 
 // Strided rows of at least this many bytes take the wide form (one row's tiles
 // per G workgroups), shorter ones the narrow form (rows flattened into units):
@@ -670,8 +672,10 @@ int indexed_args(const void *in_displs, const void *io_displs, uint64_t disp_uni
 // (for a call indexed_args left as WIDE: at least one table).  The tables are
 // compared with null, never read: what a device table holds the host cannot see,
 // so G is the worst case and the vector form needs disp_unit's word for it.
+// `fetch` (the fetching ordered call's packed output, else null) joins the
+// vector form's alignment test: its blocks sit at multiples of the block's bytes.
 void indexed_plan(const void *in, const void *in_displs, const void *io, const void *io_displs, uint64_t disp_unit,
-                  uint64_t nblocks, uint64_t blocklen, int elem, StridedPlan &p) {
+                  uint64_t nblocks, uint64_t blocklen, int elem, StridedPlan &p, const void *fetch = nullptr) {
     const uint64_t esz = g_elem_size[elem];
     const uint64_t cap = t_strided_cap && t_strided_cap < kBatchMaxGroups ? t_strided_cap : kBatchMaxGroups;
     p.row_bytes = blocklen * esz;
@@ -683,7 +687,7 @@ void indexed_plan(const void *in, const void *in_displs, const void *io, const v
         p.rows_per_launch = cap / p.per;                // a block is never split between launches
     } else {
         const uint64_t all = p.row_bytes | reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(io) |
-                             (in_displs || io_displs ? disp_unit : 0);
+                             reinterpret_cast<uintptr_t>(fetch) | (in_displs || io_displs ? disp_unit : 0);
         const bool vec = esz <= 16 && (all & 15) == 0;
         const uint64_t unit = vec ? 16 : esz;
         p.form = vec ? MPIR_HIP_INDEXED_NARROW_VEC : MPIR_HIP_INDEXED_NARROW_ELEMS;
@@ -718,9 +722,10 @@ void indexed_launches(const StridedPlan &p, const void *in, const int64_t *in_di
 // A host displacement table, read before anything is enqueued: every
 // displs[k] * disp_unit must fit 64 signed bits (MPIR_HIP_EARG), and the first
 // byte of the lowest block and the last byte of the highest must be device
-// memory on `dev` (MPIR_HIP_EBUFFER).
+// memory on `dev` (MPIR_HIP_EBUFFER).  *first / *last (where asked for): those
+// two bytes' addresses.
 int indexed_host_table(const char *base, const int64_t *displs, uint64_t disp_unit, uint64_t nblocks,
-                       uint64_t row_bytes, int dev) {
+                       uint64_t row_bytes, int dev, const char **first = nullptr, const char **last = nullptr) {
     int64_t lo = displs[0], hi = displs[0];
     for (uint64_t k = 1; k < nblocks; ++k) {
         lo = std::min(lo, displs[k]);
@@ -736,6 +741,8 @@ int indexed_host_table(const char *base, const int64_t *displs, uint64_t disp_un
         int d = -1;
         if (classify_in_span(ends[k], &d, span) != LOC_DEVICE || d != dev) return MPIR_HIP_EBUFFER;
     }
+    if (first) *first = static_cast<const char *>(ends[0]);
+    if (last) *last = static_cast<const char *>(ends[1]);
     return MPIR_HIP_OK;
 }
 
@@ -938,6 +945,74 @@ int fetch_args(uint64_t count, int op, int elem, int *path) {
         return MPIR_HIP_ENOKERNEL;
     if (count > (~(uint64_t)0 >> 1) / g_elem_size[elem]) return MPIR_HIP_EARG;
     *path = !count ? MPIR_HIP_FETCH_EMPTY : copy ? MPIR_HIP_FETCH_COPY : MPIR_HIP_FETCH_TILE;
+    return MPIR_HIP_OK;
+}
+
+// ---- fetching ordered indexed calls.  The kernel of (op, elem): the pair's own,
+// or for the two byte ops the one of the element's size (null: none)
+fetch_ordered_fn fetch_ordered_kernel(int op, int elem) {
+    if (elem <= 0 || elem >= MPIR_HIP_NELEMS) return nullptr;
+    if (op == MPIR_HIP_OP_NO_OP || op == MPIR_HIP_OP_REPLACE) {
+        const uint64_t esz = g_elem_size[elem];
+        int l = 0;
+        while (l < kFetchRaggedSizes && ((uint64_t)1 << l) != esz) ++l;
+        return l < kFetchRaggedSizes ? g_fetch_ordered_bytes[op == MPIR_HIP_OP_REPLACE][l].launch : nullptr;
+    }
+    return pair_in_range(op, elem) ? g_fetch_ordered[op][elem].launch : nullptr;
+}
+
+// the argument checks MPIR_Hip_reduce_fetch_indexed_ordered makes before it
+// looks at a pointer: the ordered call's in the ordered call's order, the op's
+// kernel looked up as the fetching calls look it up.  MPIR_HIP_OK with *form
+// EMPTY or SINGLE where that settles the call (SINGLE: no table at all).
+int fetch_ordered_args(const void *in_displs, const void *io_displs, const void *order, uint64_t disp_unit,
+                       uint64_t nblocks, uint64_t blocklen, int op, int elem, int *form) {
+    if (!fetch_ordered_kernel(op, elem)) return MPIR_HIP_ENOKERNEL;
+    if (!disp_unit || disp_unit > (~(uint64_t)0 >> 1)) return MPIR_HIP_EARG;
+    *form = MPIR_HIP_INDEXED_EMPTY;
+    if (!nblocks || !blocklen) return MPIR_HIP_OK;
+    const uint64_t esz = g_elem_size[elem];
+    if (blocklen > (~(uint64_t)0 >> 1) / esz) return MPIR_HIP_EARG;
+    if (nblocks > (~(uint64_t)0 >> 1) / (blocklen * esz)) return MPIR_HIP_EARG;
+    if (!io_displs) {
+        // a packed target has no repeats to order, and gathering the origin side is
+        // not this call's job
+        if (order || (in_displs && op != MPIR_HIP_OP_NO_OP)) return MPIR_HIP_EARG;
+        *form = MPIR_HIP_INDEXED_SINGLE;
+        return MPIR_HIP_OK;
+    }
+    if (nblocks > (uint64_t)INT32_MAX) return MPIR_HIP_EARG;
+    *form = MPIR_HIP_INDEXED_WIDE;
+    return MPIR_HIP_OK;
+}
+
+// The launches of a fetching ordered plan: ordered_launches with fetch beside.
+template <class F>
+void fetch_ordered_launches(const StridedPlan &p, const void *in, const int64_t *in_displs, void *io,
+                            const int64_t *io_displs, void *fetch, const int *order, uint64_t disp_unit,
+                            uint64_t nblocks, uint64_t blocklen, F emit) {
+    ordered_launches(p, in, in_displs, io, io_displs, order, disp_unit, nblocks, blocklen,
+                     [&](const OrderedArgs &o, uint64_t groups) {
+                         return emit(FetchOrderedArgs{o, static_cast<char *>(fetch)}, groups);
+                     });
+}
+
+// A host output table beside no order table, read before anything is enqueued:
+// the caller's promise that equal entries are adjacent.  An entry equal to an
+// earlier one that is not its neighbour: MPIR_HIP_EARG.
+int fetch_ordered_host_adjacent(const int64_t *io_displs, uint64_t nblocks) {
+    std::unique_ptr<uint32_t[]> idx(new (std::nothrow) uint32_t[nblocks]);
+    if (!idx) {
+        snprintf(ctx().err, sizeof(ctx().err), "no memory to check a displacement table of %llu entries",
+                 (unsigned long long)nblocks);
+        return MPIR_HIP_ERUNTIME;
+    }
+    for (uint64_t k = 0; k < nblocks; ++k) idx[k] = (uint32_t)k;
+    std::sort(idx.get(), idx.get() + nblocks, [&](uint32_t a, uint32_t b) {
+        return io_displs[a] != io_displs[b] ? io_displs[a] < io_displs[b] : a < b;
+    });
+    for (uint64_t p = 1; p < nblocks; ++p)
+        if (io_displs[idx[p - 1]] == io_displs[idx[p]] && idx[p] != idx[p - 1] + 1) return MPIR_HIP_EARG;
     return MPIR_HIP_OK;
 }
 
@@ -2002,6 +2077,146 @@ int MPIR_Hip_reduce_fetch_ragged(const void *inbuf, void *inoutbuf, const int64_
     const hipError_t e = launch(&a, s);
     if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
     if (e != hipSuccess) rc = set_err(e, "fetch ragged launch");
+    else if (sync) rc = wait_stream(dev, s);
+    return rc;
+}
+
+int MPIR_Hip_fetch_indexed_ordered_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
+                                             const int64_t *io_displs, const void *fetchbuf, const int *order,
+                                             uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen, int op, int elem,
+                                             uint64_t out[6]) {
+    int form = 0;
+    const int rc = fetch_ordered_args(in_displs, io_displs, order, disp_unit, nblocks, blocklen, op, elem, &form);
+    if (rc != MPIR_HIP_OK) return rc;
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    out[0] = (uint64_t)form;
+    out[4] = mpir_hip::g_strided_wide.load(std::memory_order_relaxed);
+    if (form == MPIR_HIP_INDEXED_EMPTY) return MPIR_HIP_OK;
+    if (form == MPIR_HIP_INDEXED_SINGLE) {
+        // the fetch call's own plan (MPIR_Hip_fetch_plan_info)
+        uint64_t f[4];
+        const int frc = MPIR_Hip_fetch_plan_info(inbuf, inoutbuf, fetchbuf, nblocks * blocklen, op, elem, f);
+        if (frc != MPIR_HIP_OK) return frc;
+        out[1] = f[0] == MPIR_HIP_FETCH_COPY && op == MPIR_HIP_OP_REPLACE ? 2 : 1;
+        out[2] = f[1];
+        return MPIR_HIP_OK;
+    }
+    const bool no_op = op == MPIR_HIP_OP_NO_OP;
+    StridedPlan p;
+    indexed_plan(no_op ? nullptr : inbuf, no_op ? nullptr : in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen,
+                 elem, p, fetchbuf);
+    out[0] = (uint64_t)p.form;
+    out[1] = p.launches;
+    out[2] = p.groups;
+    out[3] = p.per;
+    out[5] = p.rows_per_launch;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_reduce_fetch_indexed_ordered(const void *inbuf, const int64_t *in_displs, void *inoutbuf,
+                                          const int64_t *io_displs, void *fetchbuf, const int *order, uint64_t disp_unit,
+                                          uint64_t nblocks, uint64_t blocklen, int op, int elem, void *hip_stream,
+                                          int sync) {
+    int form = 0;
+    int rc = fetch_ordered_args(in_displs, io_displs, order, disp_unit, nblocks, blocklen, op, elem, &form);
+    if (rc != MPIR_HIP_OK || form == MPIR_HIP_INDEXED_EMPTY) return rc;
+    // no table at all: the fetch call, which makes its own checks
+    if (form == MPIR_HIP_INDEXED_SINGLE)
+        return MPIR_Hip_reduce_fetch(inbuf, inoutbuf, fetchbuf, nblocks * blocklen, op, elem, hip_stream, sync);
+    ctx().err[0] = 0;
+    // Everything classified before anything is enqueued, in the ordered call's
+    // order: the bases (NO_OP never looks at inbuf or in_displs), the last byte of
+    // a packed input and of fetchbuf, then the three tables -- device memory on
+    // the operands' device or, in a synchronous call on the library stream, host
+    // memory, which is then read and checked.  A host output table also gives the
+    // target's extent, which fetchbuf must not meet, and beside no order table is
+    // held to the promise that equal entries are adjacent.
+    const bool no_op = op == MPIR_HIP_OP_NO_OP;
+    if (no_op) {
+        inbuf = nullptr;
+        in_displs = nullptr;
+    }
+    const uint64_t row_bytes = blocklen * g_elem_size[elem];
+    const uint64_t bytes = nblocks * row_bytes;
+    const char *base[3] = {static_cast<const char *>(inbuf), static_cast<char *>(inoutbuf), static_cast<char *>(fetchbuf)};
+    const void *table[3] = {in_displs, io_displs, order};
+    const size_t tbytes[3] = {(size_t)nblocks * sizeof(int64_t), (size_t)nblocks * sizeof(int64_t),
+                              (size_t)nblocks * sizeof(int)};
+    bool host_table[3] = {false, false, false};
+    int dev = -1;
+    DeviceSpan span[3];
+    for (int k = no_op ? 1 : 0; k < 3; ++k) {
+        int d = -1;
+        if (classify_in_span(base[k], &d, span[k]) != LOC_DEVICE || (dev >= 0 && d != dev)) return MPIR_HIP_EBUFFER;
+        dev = d;
+        if ((k == 2 || !table[k]) && (classify_in_span(base[k] + (bytes - 1), &d, span[k]) != LOC_DEVICE || d != dev))
+            return MPIR_HIP_EBUFFER;
+    }
+    for (int k = 0; k < 3; ++k) {
+        if (!table[k]) continue;
+        if (table_on_device(table[k], tbytes[k], &dev, &rc)) {
+            if (rc != MPIR_HIP_OK) return rc;
+            continue;
+        }
+        if (hip_stream || !sync) return MPIR_HIP_EBUFFER;       // a host table would be read after the call returned
+        host_table[k] = true;
+        if (k == 0) {
+            rc = indexed_host_table(base[0], in_displs, disp_unit, nblocks, row_bytes, dev);
+        } else if (k == 1) {
+            const char *first = nullptr, *last = nullptr;
+            rc = indexed_host_table(base[1], io_displs, disp_unit, nblocks, row_bytes, dev, &first, &last);
+            if (rc != MPIR_HIP_OK) return rc;
+            // the fetched bytes must not land on a target block: anywhere in the blocks' extent is refused
+            const uintptr_t f0 = reinterpret_cast<uintptr_t>(fetchbuf), f1 = f0 + (bytes - 1);
+            if (f0 <= reinterpret_cast<uintptr_t>(last) && reinterpret_cast<uintptr_t>(first) <= f1) return MPIR_HIP_EBUFFER;
+            if (!order) rc = fetch_ordered_host_adjacent(io_displs, nblocks);
+        } else {
+            rc = ordered_host_order(order, host_table[1] ? io_displs : nullptr, nblocks);
+        }
+        if (rc != MPIR_HIP_OK) return rc;
+    }
+    StridedPlan p;
+    indexed_plan(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, elem, p, fetchbuf);
+    if (p.form == MPIR_HIP_INDEXED_WIDE && p.per > kBatchMaxGroups) {
+        snprintf(ctx().err, sizeof(ctx().err), "an indexed block needs more workgroups than one launch holds");
+        return MPIR_HIP_ERUNTIME;
+    }
+    DeviceScope on(dev);
+    if (!on.ok()) return on.err();
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!s) rc = get_stream(dev, S_MAIN, &s);
+    if (rc != MPIR_HIP_OK) return rc;
+    if (host_table[0] || host_table[1] || host_table[2]) {
+        // host tables into the thread's table buffer, stream-ordered ahead of the
+        // kernels; the order table's ints last, so the displacements stay 8-byte aligned
+        size_t total = 0;
+        for (int k = 0; k < 3; ++k) total += host_table[k] ? tbytes[k] : 0;
+        char *buf = nullptr;
+        rc = get_tables(dev, total, &buf);
+        if (rc != MPIR_HIP_OK) return rc;               // (nothing of this call is queued yet)
+        for (int k = 0; k < 3; ++k) {
+            if (!host_table[k]) continue;
+            const hipError_t ce = hipMemcpyAsync(buf, table[k], tbytes[k], hipMemcpyHostToDevice, s);
+            if (ce != hipSuccess) {
+                // (another table's copy may be queued on the library stream)
+                ctx().dev[dev].main_pending = true;
+                return set_err(ce, "fetching ordered indexed table copy");
+            }
+            table[k] = buf;
+            buf += tbytes[k];
+        }
+    }
+    hipError_t e = hipSuccess;
+    const fetch_ordered_fn launch = fetch_ordered_kernel(op, elem);
+    fetch_ordered_launches(p, inbuf, static_cast<const int64_t *>(table[0]), inoutbuf,
+                           static_cast<const int64_t *>(table[1]), fetchbuf, static_cast<const int *>(table[2]), disp_unit,
+                           nblocks, blocklen, [&](const FetchOrderedArgs &a, uint64_t groups) {
+                               e = launch(&a, groups, s);
+                               return e == hipSuccess;
+                           });
+    // (launches made before one that failed are still queued on the library stream)
+    if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
+    if (e != hipSuccess) rc = set_err(e, "fetching ordered indexed launch");
     else if (sync) rc = wait_stream(dev, s);
     return rc;
 }

@@ -40,6 +40,7 @@ typedef hipError_t (*ordered_fn)(const OrderedArgs *, uint64_t, hipStream_t);
 typedef hipError_t (*ragged_fn)(const RaggedArgs *, hipStream_t);
 typedef void (*fplan_fn)(const FetchArgs *, FetchPlan *);
 typedef hipError_t (*fetch_ragged_fn)(const FetchRaggedArgs *, hipStream_t);
+typedef hipError_t (*fetch_ordered_fn)(const FetchOrderedArgs *, uint64_t, hipStream_t);
 
 // plan: plan_reduce<T> (reduce_kernels.hpp) for the classes whose launcher is
 // launch_reduce -- the kernel, grid and argument bytes the direct AQL dispatch
@@ -87,6 +88,13 @@ struct RaggedEntry { ragged_fn launch; };
 // bytes (reg_fetch_ragged_bytes.hip): they take every element class of that size.
 struct FetchRaggedEntry { fetch_ragged_fn launch; };
 constexpr int kFetchRaggedSizes = 6;
+// g_fetch_ordered[op][elem], likewise: launch_fetch_indexed_ordered<Op, T>, one
+// launch of k_reduce_fetch_indexed_ordered over a range of sorted positions
+// (MPIR_Hip_reduce_fetch_indexed_ordered), for the pairs g_ordered holds
+// (reg_fetch_ordered<>, from the reg_fetch_ordered_*.hip units).
+// g_fetch_ordered_bytes[which][log2 size]: the same kernel over the two byte
+// functors, laid out as g_fetch_ragged_bytes is (reg_fetch_ordered_bytes.hip).
+struct FetchOrderedEntry { fetch_ordered_fn launch; };
 
 // float / double SUM and PROD on the host: the SSE instruction itself.  The
 // reference's loop `a[i] = a[i] + b[i]` (opsum.c:21-76, gcc -O2) is an
@@ -162,6 +170,8 @@ extern OrderedEntry g_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern RaggedEntry g_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchRaggedEntry g_fetch_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchRaggedEntry g_fetch_ragged_bytes[2][kFetchRaggedSizes];
+extern FetchOrderedEntry g_fetch_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern FetchOrderedEntry g_fetch_ordered_bytes[2][kFetchRaggedSizes];
 constexpr int kMultiMaxP = 8;
 extern multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 
@@ -222,6 +232,19 @@ void reg_fetch_ragged_bytes() {
     static_assert(LOG2 >= 0 && LOG2 < kFetchRaggedSizes, "element sizes 1 to 32 bytes");
     g_fetch_ragged_bytes[0][LOG2] = FetchRaggedEntry{&launch_fetch_ragged<OpFetchNoOp, RawBytes<(1 << LOG2)>>};
     g_fetch_ragged_bytes[1][LOG2] = FetchRaggedEntry{&launch_fetch_ragged<OpFetchSwap, RawBytes<(1 << LOG2)>>};
+}
+// the fetching ordered indexed kernel of the pairs reg_ordered<> registers, from
+// the reg_fetch_ordered_*.hip units
+template <class Op, class T>
+void reg_fetch_ordered(int op, int elem) {
+    g_fetch_ordered[op][elem] = FetchOrderedEntry{&launch_fetch_indexed_ordered<Op, T>};
+}
+// ... and of MPI_NO_OP and MPI_REPLACE on elements of 1 << LOG2 bytes
+template <int LOG2>
+void reg_fetch_ordered_bytes() {
+    static_assert(LOG2 >= 0 && LOG2 < kFetchRaggedSizes, "element sizes 1 to 32 bytes");
+    g_fetch_ordered_bytes[0][LOG2] = FetchOrderedEntry{&launch_fetch_indexed_ordered<OpFetchNoOp, RawBytes<(1 << LOG2)>>};
+    g_fetch_ordered_bytes[1][LOG2] = FetchOrderedEntry{&launch_fetch_indexed_ordered<OpFetchSwap, RawBytes<(1 << LOG2)>>};
 }
 template <class Op, class T>
 void reg_multi(int op, int elem) {

@@ -1154,42 +1154,130 @@ struct OrderedArgs {
     uint32_t pad_;
 };
 
+// The helpers below serve two kernels.  Fetch = false is k_reduce_indexed_ordered
+// as described above.  Fetch = true is k_reduce_fetch_indexed_ordered (its own
+// section, below): before every combine the running value goes to block
+// k's place in a packed `fetch` buffer, a null `order` is the identity, and Op may
+// be one of the two byte functors (OpFetchNoOp: no input is read and the target
+// is never stored; OpFetchSwap: the input's bytes become the running value) over
+// T = RawBytes<size>.  Everything the fetching form adds sits under `if constexpr
+// (Fetch)`, so the Fetch = false instantiations are the code they were.
+struct OpFetchNoOp;
+struct OpFetchSwap;
+template <int N>
+struct RawBytes;
+
 // the block at sorted position p (p < nblocks), clamped into the tables
+template <bool Fetch = false>
 __device__ __forceinline__ uint32_t ordered_block(const OrderedArgs &a, uint32_t p) {
+    if constexpr (Fetch)
+        if (!a.order) return p;                             // (uniform: a kernel argument)
     const uint32_t k = (uint32_t)a.order[p];
     return k < a.nblocks ? k : a.nblocks - 1;
 }
 
-// Element i of the run headed by position p (block k0, displacement d0, target
-// block at io): loaded once, every block of the run combined in, stored once.
+// combine16 for the ops of either kernel
 template <class Op, class T>
-__device__ __forceinline__ void ordered_elem_run(const OrderedArgs &a, uint32_t p, uint32_t k0, int64_t d0, char *io,
-                                                 uint64_t row_bytes, uint64_t i) {
-    Op op;
-    T x, y;
-    __builtin_memcpy(&x, io + i * sizeof(T), sizeof(T));
-    uint32_t k = k0;
-    for (uint32_t q = p;;) {
-        const char *in = a.in + indexed_off(a.in_displs, k, a.disp_unit, row_bytes);
-        __builtin_memcpy(&y, in + i * sizeof(T), sizeof(T));
-        x = op(x, y);
-        if (++q >= a.nblocks) break;
-        k = ordered_block(a, q);
-        if (a.io_displs[k] != d0) break;
-    }
-    __builtin_memcpy(io + i * sizeof(T), &x, sizeof(T));
+__device__ __forceinline__ u32x4 ordered_combine16(u32x4 x, u32x4 y) {
+    if constexpr (__is_same(Op, OpFetchNoOp)) return x;
+    else if constexpr (__is_same(Op, OpFetchSwap)) return y;
+    else return combine16<Op, T>(x, y);
 }
 
-template <class Op, class T>
-__device__ __forceinline__ void reduce_ordered_wide(const OrderedArgs &a) {
+// N bytes of no type to dst (any alignment), nt like every store to fetchbuf
+template <class Raw>
+__device__ __forceinline__ void ordered_fetch_store(char *dst, const Raw &x) {
+    typedef decltype(Raw::v) __attribute__((aligned(1))) unaligned_t;
+    __builtin_nontemporal_store(x.v, reinterpret_cast<unaligned_t *>(dst));
+}
+
+// Element i of the run headed by position p (block k0, displacement d0, target
+// block at io): loaded once, every block of the run combined in, stored once.
+// Fetch: the element's bytes as they stand before block k's combine go to block
+// k of `fetch` -- for the head the target's own bytes, never a value of type T.
+template <class Op, class T, bool Fetch = false>
+__device__ __forceinline__ void ordered_elem_run(const OrderedArgs &a, uint32_t p, uint32_t k0, int64_t d0, char *io,
+                                                 uint64_t row_bytes, uint64_t i, char *fetch = nullptr) {
+    if constexpr (Fetch) {
+        typedef RawBytes<(int)sizeof(T)> Raw;
+        constexpr bool no_op = __is_same(Op, OpFetchNoOp), swap = __is_same(Op, OpFetchSwap);
+        Raw x;
+        __builtin_memcpy(&x, io + i * sizeof(T), sizeof(T));
+        uint32_t k = k0;
+        for (uint32_t q = p;;) {
+            ordered_fetch_store(fetch + (uint64_t)k * row_bytes + i * sizeof(T), x);
+            if constexpr (!no_op) {
+                const char *in = a.in + indexed_off(a.in_displs, k, a.disp_unit, row_bytes);
+                if constexpr (swap) {
+                    __builtin_memcpy(&x, in + i * sizeof(T), sizeof(T));
+                } else {
+                    Op op;
+                    T y;
+                    __builtin_memcpy(&y, in + i * sizeof(T), sizeof(T));
+                    x = __builtin_bit_cast(Raw, op(__builtin_bit_cast(T, x), y));
+                }
+            }
+            if (++q >= a.nblocks) break;
+            k = ordered_block<true>(a, q);
+            if (a.io_displs[k] != d0) break;
+        }
+        if constexpr (!no_op) __builtin_memcpy(io + i * sizeof(T), &x, sizeof(T));
+    } else {
+        Op op;
+        T x, y;
+        __builtin_memcpy(&x, io + i * sizeof(T), sizeof(T));
+        uint32_t k = k0;
+        for (uint32_t q = p;;) {
+            const char *in = a.in + indexed_off(a.in_displs, k, a.disp_unit, row_bytes);
+            __builtin_memcpy(&y, in + i * sizeof(T), sizeof(T));
+            x = op(x, y);
+            if (++q >= a.nblocks) break;
+            k = ordered_block(a, q);
+            if (a.io_displs[k] != d0) break;
+        }
+        __builtin_memcpy(io + i * sizeof(T), &x, sizeof(T));
+    }
+}
+
+// A workgroup's tile of the running value (x: the lane's kVecPerLane vectors at
+// byte offsets wb + u * 1024 of the nrec-byte tile at io_tile) out to `fe`, the
+// same tile of a block of fetch: through a descriptor bounded like the target's
+// (lanes outside the tile are dropped) where fe shares the target's 16-byte
+// phase, else element by element
+// under the guard the off-phase input path has.  nt stores both.
+template <class T>
+__device__ __forceinline__ void ordered_wide_fetch(const u32x4 (&x)[kVecPerLane], char *fe, const char *io_tile, int nrec,
+                                                   int wb) {
+    if (((reinterpret_cast<uintptr_t>(fe) ^ reinterpret_cast<uintptr_t>(io_tile)) & 15) == 0) {
+        __amdgpu_buffer_rsrc_t rfe = __builtin_amdgcn_make_buffer_rsrc((void *)fe, 0, nrec, 0x00020000);
+#pragma unroll
+        for (int u = 0; u < kVecPerLane; ++u) store16(x[u], rfe, wb + u * 1024, false);
+    } else {
+#pragma unroll
+        for (int u = 0; u < kVecPerLane; ++u) {
+            const int off = wb + u * 1024;
+            if ((unsigned)off < (unsigned)nrec) {
+                const Pack16<T> v = __builtin_bit_cast(Pack16<T>, x[u]);
+#pragma unroll
+                for (int e = 0; e < (int)(16 / sizeof(T)); ++e)
+                    ordered_fetch_store(fe + off + e * (int)sizeof(T),
+                                        __builtin_bit_cast(RawBytes<(int)sizeof(T)>, v.e[e]));
+            }
+        }
+    }
+}
+
+template <class Op, class T, bool Fetch = false>
+__device__ __forceinline__ void reduce_ordered_wide(const OrderedArgs &a, char *fetch = nullptr) {
+    constexpr bool no_op = __is_same(Op, OpFetchNoOp);
     const uint32_t r = blockIdx.x / a.per;
     if (r >= a.nrows) return;
     const uint32_t p = a.pos0 + r;
     const uint64_t tile = blockIdx.x - r * a.per;
     const uint64_t row_bytes = a.blocklen * sizeof(T);
-    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ordered_block(a, p));
+    const uint32_t k0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)ordered_block<Fetch>(a, p));
     const int64_t d0 = (int64_t)wave_uniform64((uint64_t)a.io_displs[k0]);
-    if (p && a.io_displs[ordered_block(a, p - 1)] == d0) return;           // not a head
+    if (p && a.io_displs[ordered_block<Fetch>(a, p - 1)] == d0) return;    // not a head
     char *io = a.io + (uint64_t)d0 * a.disp_unit;
     // the target's own split: an input block's alignment decides only how it is read
     const SegSplit s = seg_split<T>(io, io, a.blocklen);
@@ -1212,44 +1300,51 @@ __device__ __forceinline__ void reduce_ordered_wide(const OrderedArgs &a) {
                     x[u] = __builtin_amdgcn_raw_buffer_load_b128(rio, wb + u * 1024, 0, kCachePolicyNT);
                 uint32_t k = k0;
                 for (uint32_t q = p;;) {
-                    const uint64_t oi = wave_uniform64(indexed_off(a.in_displs, k, a.disp_unit, row_bytes));
-                    const char *in = a.in + oi + s.head_bytes + lo;
-                    if (((reinterpret_cast<uintptr_t>(in) ^ reinterpret_cast<uintptr_t>(iov + lo)) & 15) == 0) {
-                        __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)in, 0, nrec, 0x00020000);
-                        u32x4 y[kVecPerLane];
+                    if constexpr (Fetch)
+                        ordered_wide_fetch<T>(x, fetch + (uint64_t)k * row_bytes + s.head_bytes + lo, iov + lo, nrec, wb);
+                    if constexpr (!no_op) {
+                        const uint64_t oi = wave_uniform64(indexed_off(a.in_displs, k, a.disp_unit, row_bytes));
+                        const char *in = a.in + oi + s.head_bytes + lo;
+                        if (((reinterpret_cast<uintptr_t>(in) ^ reinterpret_cast<uintptr_t>(iov + lo)) & 15) == 0) {
+                            __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *)in, 0, nrec, 0x00020000);
+                            u32x4 y[kVecPerLane];
 #pragma unroll
-                        for (int u = 0; u < kVecPerLane; ++u)
-                            y[u] = __builtin_amdgcn_raw_buffer_load_b128(rin, wb + u * 1024, 0, kCachePolicyNT);
+                            for (int u = 0; u < kVecPerLane; ++u)
+                                y[u] = __builtin_amdgcn_raw_buffer_load_b128(rin, wb + u * 1024, 0, kCachePolicyNT);
 #pragma unroll
-                        for (int u = 0; u < kVecPerLane; ++u) x[u] = combine16<Op, T>(x[u], y[u]);
-                    } else {
-                        // an input block off the target's 16-byte phase: its elements one
-                        // by one, only where the lane's vector lies inside the tile
+                            for (int u = 0; u < kVecPerLane; ++u) x[u] = ordered_combine16<Op, T>(x[u], y[u]);
+                        } else {
+                            // an input block off the target's 16-byte phase: its elements one
+                            // by one, only where the lane's vector lies inside the tile
 #pragma unroll
-                        for (int u = 0; u < kVecPerLane; ++u) {
-                            const int off = wb + u * 1024;
-                            if ((unsigned)off < (unsigned)nrec) {
-                                Pack16<T> y;
+                            for (int u = 0; u < kVecPerLane; ++u) {
+                                const int off = wb + u * 1024;
+                                if ((unsigned)off < (unsigned)nrec) {
+                                    Pack16<T> y;
 #pragma unroll
-                                for (int e = 0; e < (int)(16 / sizeof(T)); ++e)
-                                    __builtin_memcpy(&y.e[e], in + off + e * (int)sizeof(T), sizeof(T));
-                                x[u] = combine16<Op, T>(x[u], __builtin_bit_cast(u32x4, y));
+                                    for (int e = 0; e < (int)(16 / sizeof(T)); ++e)
+                                        __builtin_memcpy(&y.e[e], in + off + e * (int)sizeof(T), sizeof(T));
+                                    x[u] = ordered_combine16<Op, T>(x[u], __builtin_bit_cast(u32x4, y));
+                                }
                             }
                         }
                     }
                     if (++q >= a.nblocks) break;
-                    k = (uint32_t)__builtin_amdgcn_readfirstlane((int)ordered_block(a, q));
+                    k = (uint32_t)__builtin_amdgcn_readfirstlane((int)ordered_block<Fetch>(a, q));
                     if (a.io_displs[k] != d0) break;
                 }
+                if constexpr (!no_op) {
 #pragma unroll
-                for (int u = 0; u < kVecPerLane; ++u) store16(x[u], rio, wb + u * 1024, false);
+                    for (int u = 0; u < kVecPerLane; ++u) store16(x[u], rio, wb + u * 1024, false);
+                }
             }
             if (tile == 0) {
                 // the head and tail elements, a lane each as in reduce_seg
                 const unsigned t = threadIdx.x;
-                if (t < s.nhead) ordered_elem_run<Op, T>(a, p, k0, d0, io, row_bytes, t);
+                if (t < s.nhead) ordered_elem_run<Op, T, Fetch>(a, p, k0, d0, io, row_bytes, t, fetch);
                 else if (t >= 64 && t - 64 < s.ntail)
-                    ordered_elem_run<Op, T>(a, p, k0, d0, io, row_bytes, (s.head_bytes + s.vbytes) / sizeof(T) + (t - 64));
+                    ordered_elem_run<Op, T, Fetch>(a, p, k0, d0, io, row_bytes,
+                                                   (s.head_bytes + s.vbytes) / sizeof(T) + (t - 64), fetch);
             }
             return;
         }
@@ -1257,14 +1352,16 @@ __device__ __forceinline__ void reduce_ordered_wide(const OrderedArgs &a) {
     constexpr uint64_t per = kTileBytes / sizeof(T);
     const uint64_t base = tile * per;
     const uint64_t end = base + per < a.blocklen ? base + per : a.blocklen;
-    for (uint64_t i = base + threadIdx.x; i < end; i += kThreads) ordered_elem_run<Op, T>(a, p, k0, d0, io, row_bytes, i);
+    for (uint64_t i = base + threadIdx.x; i < end; i += kThreads)
+        ordered_elem_run<Op, T, Fetch>(a, p, k0, d0, io, row_bytes, i, fetch);
 }
 
 // sorted positions the narrow vector form looks ahead of a run's current end
 constexpr int kOrderedAhead = 4;
 
-template <class Op, class T>
-__device__ __forceinline__ void reduce_ordered_narrow(const OrderedArgs &a) {
+template <class Op, class T, bool Fetch = false>
+__device__ __forceinline__ void reduce_ordered_narrow(const OrderedArgs &a, char *fetch = nullptr) {
+    constexpr bool no_op = __is_same(Op, OpFetchNoOp);
     const uint32_t upr = a.per;                             // units per block
     const uint64_t row_bytes = a.blocklen * sizeof(T);
     const unsigned t = threadIdx.x;
@@ -1292,13 +1389,14 @@ __device__ __forceinline__ void reduce_ordered_narrow(const OrderedArgs &a) {
                 off[j] = (uint64_t)(c - q * upr) * 16;
             }
 #pragma unroll
-            for (int j = 0; j < per_lane; ++j) k[j] = ordered_block(a, pos[j]);
+            for (int j = 0; j < per_lane; ++j) k[j] = ordered_block<Fetch>(a, pos[j]);
 #pragma unroll
-            for (int j = 0; j < per_lane; ++j) kp[j] = ordered_block(a, pos[j] ? pos[j] - 1 : 0);
+            for (int j = 0; j < per_lane; ++j) kp[j] = ordered_block<Fetch>(a, pos[j] ? pos[j] - 1 : 0);
             // (the position after, with the same loads: whether a run goes on at all is
             // then known without another round trip, and a run of one ends here)
 #pragma unroll
-            for (int j = 0; j < per_lane; ++j) kn[j] = ordered_block(a, pos[j] + 1 < a.nblocks ? pos[j] + 1 : pos[j]);
+            for (int j = 0; j < per_lane; ++j)
+                kn[j] = ordered_block<Fetch>(a, pos[j] + 1 < a.nblocks ? pos[j] + 1 : pos[j]);
 #pragma unroll
             for (int j = 0; j < per_lane; ++j) d[j] = a.io_displs[k[j]];
 #pragma unroll
@@ -1310,7 +1408,7 @@ __device__ __forceinline__ void reduce_ordered_narrow(const OrderedArgs &a) {
                 head[j] = head[j] && (pos[j] == 0 || d[j] != dp[j]);
                 oi[j] = (uint64_t)k[j] * row_bytes;         // the packed place
             }
-            if (a.in_displs) {
+            if (!no_op && a.in_displs) {
                 int64_t di[per_lane];
 #pragma unroll
                 for (int j = 0; j < per_lane; ++j) di[j] = a.in_displs[k[j]];
@@ -1324,13 +1422,18 @@ __device__ __forceinline__ void reduce_ordered_narrow(const OrderedArgs &a) {
                 x[j] = y[j] = u32x4{0, 0, 0, 0};
                 if (head[j]) {
                     x[j] = __builtin_nontemporal_load((const global_u32x4 *)(a.io + (uint64_t)d[j] * a.disp_unit + off[j]));
-                    y[j] = __builtin_nontemporal_load((const global_u32x4 *)(a.in + oi[j] + off[j]));
+                    if constexpr (!no_op)
+                        y[j] = __builtin_nontemporal_load((const global_u32x4 *)(a.in + oi[j] + off[j]));
                 }
             }
 #pragma unroll
             for (int j = 0; j < per_lane; ++j) {
                 if (!head[j]) continue;
-                u32x4 v = combine16<Op, T>(x[j], y[j]);
+                // (Fetch: the target's own bytes to the head block's place, then every
+                // later block of the run gets v as it stands before its combine)
+                if constexpr (Fetch)
+                    __builtin_nontemporal_store(x[j], (global_u32x4 *)(fetch + (uint64_t)k[j] * row_bytes + off[j]));
+                u32x4 v = ordered_combine16<Op, T>(x[j], y[j]);
                 // the rest of the run, kOrderedAhead positions at a time: their order
                 // entries, then their displacements, then the data of those that still
                 // belong to the run issue together (a position past the table is
@@ -1345,23 +1448,30 @@ __device__ __forceinline__ void reduce_ordered_narrow(const OrderedArgs &a) {
                     bool in_run[kOrderedAhead];
 #pragma unroll
                     for (int i = 0; i < kOrderedAhead; ++i)
-                        kq[i] = ordered_block(a, q + i < a.nblocks ? q + i : a.nblocks - 1);
+                        kq[i] = ordered_block<Fetch>(a, q + i < a.nblocks ? q + i : a.nblocks - 1);
 #pragma unroll
                     for (int i = 0; i < kOrderedAhead; ++i) dq[i] = a.io_displs[kq[i]];
 #pragma unroll
-                    for (int i = 0; i < kOrderedAhead; ++i) oq[i] = indexed_off(a.in_displs, kq[i], a.disp_unit, row_bytes);
+                    for (int i = 0; i < kOrderedAhead; ++i)
+                        oq[i] = no_op ? 0 : indexed_off(a.in_displs, kq[i], a.disp_unit, row_bytes);
 #pragma unroll
                     for (int i = 0; i < kOrderedAhead; ++i) {
                         more = more && q + i < a.nblocks && dq[i] == d[j];
                         w[i] = u32x4{0, 0, 0, 0};
-                        if (more) w[i] = __builtin_nontemporal_load((const global_u32x4 *)(a.in + oq[i] + off[j]));
+                        if constexpr (!no_op)
+                            if (more) w[i] = __builtin_nontemporal_load((const global_u32x4 *)(a.in + oq[i] + off[j]));
                         in_run[i] = more;
                     }
 #pragma unroll
                     for (int i = 0; i < kOrderedAhead; ++i)
-                        if (in_run[i]) v = combine16<Op, T>(v, w[i]);
+                        if (in_run[i]) {
+                            if constexpr (Fetch)
+                                __builtin_nontemporal_store(v, (global_u32x4 *)(fetch + (uint64_t)kq[i] * row_bytes + off[j]));
+                            v = ordered_combine16<Op, T>(v, w[i]);
+                        }
                 }
-                __builtin_nontemporal_store(v, (global_u32x4 *)(a.io + (uint64_t)d[j] * a.disp_unit + off[j]));
+                if constexpr (!no_op)
+                    __builtin_nontemporal_store(v, (global_u32x4 *)(a.io + (uint64_t)d[j] * a.disp_unit + off[j]));
             }
             return;
         }
@@ -1376,10 +1486,10 @@ __device__ __forceinline__ void reduce_ordered_narrow(const OrderedArgs &a) {
         const uint64_t r = row0 + q;
         if (r >= a.nrows) break;                            // positions only grow with u
         const uint32_t p = a.pos0 + (uint32_t)r;
-        const uint32_t k0 = ordered_block(a, p);
+        const uint32_t k0 = ordered_block<Fetch>(a, p);
         const int64_t d0 = a.io_displs[k0];
-        if (p && a.io_displs[ordered_block(a, p - 1)] == d0) continue;      // not a head
-        ordered_elem_run<Op, T>(a, p, k0, d0, a.io + (uint64_t)d0 * a.disp_unit, row_bytes, c - q * upr);
+        if (p && a.io_displs[ordered_block<Fetch>(a, p - 1)] == d0) continue;   // not a head
+        ordered_elem_run<Op, T, Fetch>(a, p, k0, d0, a.io + (uint64_t)d0 * a.disp_unit, row_bytes, c - q * upr, fetch);
     }
 }
 
@@ -1396,6 +1506,72 @@ hipError_t launch_indexed_ordered(const OrderedArgs *a, uint64_t groups, hipStre
         (uint64_t)a->pos0 + a->nrows > a->nblocks || groups < 1 || groups > kBatchMaxGroups)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL((k_reduce_indexed_ordered<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+// ============================================================================
+// Fetching ordered indexed reductions (MPIR_Hip_reduce_fetch_indexed_ordered):
+// the ordered kernel with every intermediate value of a run handed out.  The
+// call is MPIX_Reduce_local_fetch block by block in table order: block k of the
+// packed `fetch` buffer receives the bytes target block io_displs[k] held after
+// contributions 0 .. k - 1 and before contribution k -- what each of the
+// MPI_Fetch_and_op / MPI_Get_accumulate operations a target has queued for one
+// location must answer, a deterministic fetch-and-add, an exclusive scan by key.
+//
+// The ordered kernel already holds that value in registers at every step, so
+// this kernel is the same functions with Fetch = true: the same head test, run
+// loop, launches (pos0 / nrows / nblocks), split of a wide target and clamped
+// table reads.  What it adds:
+//
+//   * One value: the registers stored to fetch and the registers combined are
+//     the same ones.  The target is loaded once per run and stored once per run,
+//     for MPI_NO_OP never.
+//   * The head's store is the target's own bytes (a vector, or an element's
+//     RawBytes), so NaN payloads and padding arrive as they were; a later block's
+//     store is the bytes the ordered kernel would have stored to the target had
+//     the run ended there.
+//   * NARROW_VEC: the head stores x to fetch + k * row_bytes + off before its
+//     first combine; in the look-ahead loop the four table and data loads still
+//     issue together, and between the ordered combines v goes to block kq[i]'s
+//     place.  fetch must be a multiple of 16 for this form (the host's plan).
+//   * WIDE: ordered_wide_fetch before each ordered_wide_combine.  Packed fetch
+//     blocks sit at k * row_bytes, so one run may take the descriptor stores for
+//     some blocks and the element stores for others.
+//   * A null `order` is the identity (sorted position p is block p): the caller's
+//     promise that equal entries of io_displs are adjacent.  The test is on a
+//     kernel argument, uniform.
+//   * MPI_NO_OP and MPI_REPLACE are OpFetchNoOp / OpFetchSwap over
+//     RawBytes<size>, as in k_reduce_fetch_ragged: NO_OP reads neither `in` nor
+//     in_displs and stores no target (every block of a run receives the same old
+//     bytes); REPLACE hands block k the previous block's input bytes.
+//
+// Block k's place in fetch belongs to the one lane that owns that piece of k's
+// run, so no two lanes write one byte of fetch.  Every k is clamped below
+// nblocks: whatever a device order table holds, stores stay inside fetch's
+// nblocks x row_bytes and inside target blocks the displacement table names.
+//
+// No LDS, no scratch, no gridDim.  88 bytes of kernel arguments.  Every store to
+// fetch and every tile and vector store is nt.
+// ============================================================================
+struct FetchOrderedArgs {
+    OrderedArgs o;              // as for k_reduce_indexed_ordered, but `order` may be null (identity)
+    char *fetch;                // packed by block number: block k at k * the block's bytes
+};
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_reduce_fetch_indexed_ordered(FetchOrderedArgs a) {
+    if (a.o.form == MPIR_HIP_INDEXED_WIDE) reduce_ordered_wide<Op, T, true>(a.o, a.fetch);
+    else reduce_ordered_narrow<Op, T, true>(a.o, a.fetch);
+}
+
+// one launch: `groups` workgroups over sorted positions [pos0, pos0 + nrows)
+template <class Op, class T>
+hipError_t launch_fetch_indexed_ordered(const FetchOrderedArgs *a, uint64_t groups, hipStream_t s) {
+    const OrderedArgs &o = a->o;
+    if (!o.nrows || !o.per || !o.blocklen || !o.disp_unit || !o.io_displs || !a->fetch ||
+        (uint64_t)o.pos0 + o.nrows > o.nblocks || groups < 1 || groups > kBatchMaxGroups)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_reduce_fetch_indexed_ordered<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
     return hipGetLastError();
 }
 

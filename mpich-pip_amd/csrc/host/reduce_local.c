@@ -1016,12 +1016,75 @@ int MPIX_Reduce_local_fetch_ragged(const void *inbuf, void *inoutbuf, const MPI_
     return rc;
 }
 
+/* The op rule of the fetching calls whose byte ops are kernels (the ragged and
+ * the ordered indexed one): *opidx and *elem of (datatype, op), or the error
+ * class with the detail set. */
+static int fetch_op_elem(MPI_Datatype datatype, MPI_Op op, int *opidx, int *elem)
+{
+    const int no_op = op == MPI_NO_OP, copy = no_op || op == MPI_REPLACE;
+    int mpi_errno;
+    /* MPIR_ERRTEST_OP_GACC (mpir_err.h:528-539): MPI_NO_OP and MPI_REPLACE pass,
+     * a user op does not */
+    if (op == MPI_OP_NULL) {
+        MPIR_Err_set_detail("Null MPI_Op");
+        return MPI_ERR_OP;
+    }
+    if (HANDLE_GET_MPI_KIND(op) != MPIR_OP_OBJ_KIND || HANDLE_GET_KIND(op) == HANDLE_KIND_INVALID ||
+        (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN && !user_op_get(op)) ||
+        (HANDLE_GET_KIND(op) == HANDLE_KIND_BUILTIN &&
+         ((op & 0xf) >= MPIR_OP_N_BUILTIN || !MPIR_OP_HDL_TO_DTYPE_FN(op)))) {
+        MPIR_Err_set_detail("Invalid MPI_Op");
+        return MPI_ERR_OP;
+    }
+    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
+        MPIR_Err_set_detail("MPI_Op is not a predefined operation; user MPI_Op functions run on the host");
+        return MPI_ERR_OP;
+    }
+    *opidx = op & 0xf;
+    if (copy) {
+        /* the tables count elements of the datatype, so the byte ops need its
+         * element size: the described type's class, or for another builtin handle
+         * (MPI_WCHAR) a class of its size; a derived one needs MPICH's datatype engine */
+        const MPIR_Type_desc *d = MPIR_Type_lookup(datatype);
+        const unsigned h = (unsigned) datatype;
+        *elem = 0;
+        if (d) {
+            *elem = d->elem;
+        } else if ((h >> 30) == 1u && ((h >> 26) & 0xfu) == 0x3u) {     /* builtin-kind datatype: a class of its size */
+            switch ((h >> 8) & 0xffu) {
+                case 1: *elem = MPIR_HIP_U8; break;
+                case 2: *elem = MPIR_HIP_U16; break;
+                case 4: *elem = MPIR_HIP_U32; break;
+                case 8: *elem = MPIR_HIP_U64; break;
+                case 16: *elem = MPIR_HIP_CF64; break;
+                case 32: *elem = MPIR_HIP_CF80; break;
+            }
+        }
+        if (!*elem) {
+            MPIR_Err_set_detail("%s: derived datatypes are not supported by this library", no_op ? "MPI_NO_OP" : "MPI_REPLACE");
+            return MPI_ERR_TYPE;
+        }
+    } else {
+        /* MPI_Reduce_local's datatype check (reduce_local.c:179-183), then the
+         * compute switch's `default:` (LAND / LOR on floats) */
+        mpi_errno = MPIR_OP_HDL_TO_DTYPE_FN(op) (datatype);
+        if (mpi_errno != MPI_SUCCESS)
+            return mpi_errno;
+        *elem = MPIR_Op_resolve_elem(*opidx, datatype);
+        if (!*elem) {
+            MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
+            return MPI_ERR_OP;
+        }
+    }
+    return MPI_SUCCESS;
+}
+
 static int reduce_local_fetch_ragged(const void *inbuf, void *inoutbuf, const MPI_Aint * inout_displs,
                                      void *fetchbuf, const MPI_Aint * starts, MPI_Aint disp_unit, int npieces,
                                      int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
 {
     static const char *fc = "MPIX_Reduce_local_fetch_ragged";
-    const int no_op = op == MPI_NO_OP, copy = no_op || op == MPI_REPLACE;
+    const int no_op = op == MPI_NO_OP;
     int mpi_errno, opidx, elem, rc;
     uint64_t bytes;
     _Static_assert(sizeof(MPI_Aint) == sizeof(int64_t), "the shim's tables are 64-bit entries");
@@ -1031,59 +1094,9 @@ static int reduce_local_fetch_ragged(const void *inbuf, void *inoutbuf, const MP
         MPIR_Err_set_detail("negative %s %d", npieces < 0 ? "npieces" : "count", npieces < 0 ? npieces : count);
         return err_return(fc, MPI_ERR_COUNT);
     }
-    /* MPIR_ERRTEST_OP_GACC (mpir_err.h:528-539): MPI_NO_OP and MPI_REPLACE pass,
-     * a user op does not */
-    if (op == MPI_OP_NULL) {
-        MPIR_Err_set_detail("Null MPI_Op");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    if (HANDLE_GET_MPI_KIND(op) != MPIR_OP_OBJ_KIND || HANDLE_GET_KIND(op) == HANDLE_KIND_INVALID ||
-        (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN && !user_op_get(op)) ||
-        (HANDLE_GET_KIND(op) == HANDLE_KIND_BUILTIN &&
-         ((op & 0xf) >= MPIR_OP_N_BUILTIN || !MPIR_OP_HDL_TO_DTYPE_FN(op)))) {
-        MPIR_Err_set_detail("Invalid MPI_Op");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
-        MPIR_Err_set_detail("MPI_Op is not a predefined operation; user MPI_Op functions run on the host");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    opidx = op & 0xf;
-    if (copy) {
-        /* starts counts elements of the datatype, so the byte ops need its
-         * element size: the described type's class, or for another builtin handle
-         * (MPI_WCHAR) a class of its size; a derived one needs MPICH's datatype engine */
-        const MPIR_Type_desc *d = MPIR_Type_lookup(datatype);
-        const unsigned h = (unsigned) datatype;
-        elem = 0;
-        if (d) {
-            elem = d->elem;
-        } else if ((h >> 30) == 1u && ((h >> 26) & 0xfu) == 0x3u) {     /* builtin-kind datatype: a class of its size */
-            switch ((h >> 8) & 0xffu) {
-                case 1: elem = MPIR_HIP_U8; break;
-                case 2: elem = MPIR_HIP_U16; break;
-                case 4: elem = MPIR_HIP_U32; break;
-                case 8: elem = MPIR_HIP_U64; break;
-                case 16: elem = MPIR_HIP_CF64; break;
-                case 32: elem = MPIR_HIP_CF80; break;
-            }
-        }
-        if (!elem) {
-            MPIR_Err_set_detail("%s: derived datatypes are not supported by this library", no_op ? "MPI_NO_OP" : "MPI_REPLACE");
-            return err_return(fc, MPI_ERR_TYPE);
-        }
-    } else {
-        /* MPI_Reduce_local's datatype check (reduce_local.c:179-183), then the
-         * compute switch's `default:` (LAND / LOR on floats) */
-        mpi_errno = MPIR_OP_HDL_TO_DTYPE_FN(op) (datatype);
-        if (mpi_errno != MPI_SUCCESS)
-            return err_return(fc, mpi_errno);
-        elem = MPIR_Op_resolve_elem(opidx, datatype);
-        if (!elem) {
-            MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
-            return err_return(fc, MPI_ERR_OP);
-        }
-    }
+    mpi_errno = fetch_op_elem(datatype, op, &opidx, &elem);
+    if (mpi_errno != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
     /* the buffer rules of the validation block, where the ragged call has them
      * (an empty call's pointers are not looked at), MPI_NO_OP never looking at inbuf */
     if (count != 0 && !no_op && alias_check_enabled() && inbuf == inoutbuf) {
@@ -1136,6 +1149,112 @@ static int reduce_local_fetch_ragged(const void *inbuf, void *inoutbuf, const MP
     if (rc == MPIR_HIP_EARG) {
         MPIR_Err_set_detail("%s: starts is not 0, non-decreasing and ending at count, or a piece's offset does not "
                             "fit the address space", fc);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (rc != MPIR_HIP_OK) {
+        MPIR_Op_report_hip_error(fc, rc);
+        return err_return(fc, *MPIR_Op_errno_ptr());
+    }
+    return MPI_SUCCESS;
+}
+
+/* ---- MPIX_Reduce_local_fetch_indexed_ordered: the ordered fetch-and-op (see the header) */
+/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
+#pragma weak MPIR_Hip_reduce_fetch_indexed_ordered
+static int reduce_local_fetch_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                                              const MPI_Aint * inout_displs, void *fetchbuf, const int *order,
+                                              MPI_Aint disp_unit, int nblocks, int blocklen, MPI_Datatype datatype,
+                                              MPI_Op op, void *hip_stream);
+
+int MPIX_Reduce_local_fetch_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                                            const MPI_Aint * inout_displs, void *fetchbuf, const int *order,
+                                            MPI_Aint disp_unit, int nblocks, int blocklen, MPI_Datatype datatype,
+                                            MPI_Op op, void *hip_stream)
+{
+    int rc;
+    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
+    rc = reduce_local_fetch_indexed_ordered(inbuf, in_displs, inoutbuf, inout_displs, fetchbuf, order, disp_unit,
+                                            nblocks, blocklen, datatype, op, hip_stream);
+    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
+    return rc;
+}
+
+static int reduce_local_fetch_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                                              const MPI_Aint * inout_displs, void *fetchbuf, const int *order,
+                                              MPI_Aint disp_unit, int nblocks, int blocklen, MPI_Datatype datatype,
+                                              MPI_Op op, void *hip_stream)
+{
+    static const char *fc = "MPIX_Reduce_local_fetch_indexed_ordered";
+    const int no_op = op == MPI_NO_OP;
+    const int empty = nblocks == 0 || blocklen == 0;
+    int mpi_errno, opidx, elem, rc;
+    uint64_t bytes;
+    /* the ordered call's checks in the ordered call's order; where that call runs
+     * MPI_Reduce_local's validation block, this one runs the fetch call's */
+    if (nblocks < 0 || blocklen < 0) {
+        MPIR_Err_set_detail("negative %s %d", nblocks < 0 ? "nblocks" : "blocklen", nblocks < 0 ? nblocks : blocklen);
+        return err_return(fc, MPI_ERR_COUNT);
+    }
+    mpi_errno = fetch_op_elem(datatype, op, &opidx, &elem);
+    if (mpi_errno != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
+    /* the buffer rules of the validation block (an empty call's pointers are not
+     * looked at), MPI_NO_OP never looking at inbuf */
+    if (!empty && !no_op && alias_check_enabled() && inbuf == inoutbuf) {
+        MPIR_Err_set_detail("Buffers must not be aliased");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (!empty && ((!no_op && inbuf == MPI_IN_PLACE) || inoutbuf == MPI_IN_PLACE || fetchbuf == MPI_IN_PLACE)) {
+        MPIR_Err_set_detail("buffer '%s' cannot be MPI_IN_PLACE",
+                            !no_op && inbuf == MPI_IN_PLACE ? "inbuf" : inoutbuf == MPI_IN_PLACE ? "inoutbuf" : "fetchbuf");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (disp_unit <= 0) {
+        MPIR_Err_set_detail("disp_unit %ld is not positive", (long) disp_unit);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (empty)          /* no pointer or table is looked at */
+        return MPI_SUCCESS;
+    if (inout_displs == NULL && order != NULL) {
+        MPIR_Err_set_detail("an order table with no inout_displs: a packed target has no repeats to order");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (inout_displs == NULL && !no_op && in_displs != NULL) {
+        MPIR_Err_set_detail("in_displs with no inout_displs: a packed target has no repeats, and a gather on the "
+                            "origin side is not this call's job");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    /* the fetch call's rules for fetchbuf */
+    if (!fetchbuf) {
+        MPIR_Err_set_detail("Null buffer pointer 'fetchbuf'");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    bytes = (uint64_t) nblocks *(uint64_t) blocklen *MPIR_Hip_elem_size(elem);
+    /* the packed ranges, whatever MPIR_CVAR_COLL_ALIAS_CHECK says; a contiguous
+     * target is a range too */
+    if ((!no_op && !in_displs && ranges_overlap(fetchbuf, inbuf, bytes)) ||
+        (!inout_displs && ranges_overlap(fetchbuf, inoutbuf, bytes))) {
+        MPIR_Err_set_detail("fetchbuf overlaps %s",
+                            !no_op && !in_displs && ranges_overlap(fetchbuf, inbuf, bytes) ? "inbuf" : "inoutbuf");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (!MPIR_Hip_reduce_fetch_indexed_ordered) {
+        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_fetch_indexed_ordered");
+        return err_return(fc, MPI_ERR_OTHER);
+    }
+    rc = MPIR_Hip_reduce_fetch_indexed_ordered(inbuf, no_op ? NULL : (const int64_t *) in_displs, inoutbuf,
+                                               (const int64_t *) inout_displs, fetchbuf, order, (uint64_t) disp_unit,
+                                               (uint64_t) nblocks, (uint64_t) blocklen, opidx, elem, hip_stream,
+                                               hip_stream == NULL);
+    if (rc == MPIR_HIP_EBUFFER) {
+        MPIR_Err_set_detail("%s needs device-resident buffers on one device, its tables there too (host tables: the "
+                            "synchronous call only), and fetchbuf outside the target blocks' extent", fc);
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (rc == MPIR_HIP_EARG) {
+        MPIR_Err_set_detail("%s: a block's offset does not fit the address space, the order table is not a stable "
+                            "sort of inout_displs, or with no order table equal entries of inout_displs are not "
+                            "adjacent", fc);
         return err_return(fc, MPI_ERR_ARG);
     }
     if (rc != MPIR_HIP_OK) {

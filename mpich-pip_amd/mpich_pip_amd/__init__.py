@@ -120,6 +120,8 @@ EXPORTED_SYMBOLS = [
     "MPIX_Reduce_local_order", "MPIX_Reduce_local_order_worksize", "MPIR_Hip_order_build", "MPIR_Hip_order_worksize",
     "MPIX_Reduce_local_ragged", "MPIR_Hip_reduce_ragged", "MPIR_Hip_ragged_plan_info",
     "MPIX_Reduce_local_fetch_ragged", "MPIR_Hip_reduce_fetch_ragged", "MPIR_Hip_fetch_ragged_plan_info",
+    "MPIX_Reduce_local_fetch_indexed_ordered", "MPIR_Hip_reduce_fetch_indexed_ordered",
+    "MPIR_Hip_fetch_indexed_ordered_plan_info",
     # device collectives (include/mpix_hip_coll.h)
     "MPIX_Hip_comm_get_unique_id", "MPIX_Hip_comm_create", "MPIX_Hip_comm_create_loopback",
     "MPIX_Hip_comm_free", "MPIX_Hip_comm_rank", "MPIX_Hip_comm_size",
@@ -237,6 +239,13 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.MPIR_Hip_reduce_fetch_ragged.restype = i32
     lib.MPIR_Hip_fetch_ragged_plan_info.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, ctypes.POINTER(u64)]
     lib.MPIR_Hip_fetch_ragged_plan_info.restype = i32
+    lib.MPIX_Reduce_local_fetch_indexed_ordered.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_long, i32, i32, i32, i32, vp]
+    lib.MPIX_Reduce_local_fetch_indexed_ordered.restype = i32
+    lib.MPIR_Hip_reduce_fetch_indexed_ordered.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, vp, i32]
+    lib.MPIR_Hip_reduce_fetch_indexed_ordered.restype = i32
+    lib.MPIR_Hip_fetch_indexed_ordered_plan_info.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, u64, i32, i32,
+                                                             ctypes.POINTER(u64)]
+    lib.MPIR_Hip_fetch_indexed_ordered_plan_info.restype = i32
     lib.MPIX_Hip_comm_get_unique_id.argtypes = [vp]
     lib.MPIX_Hip_comm_get_unique_id.restype = i32
     lib.MPIX_Hip_comm_create.argtypes = [vp, i32, i32, ctypes.POINTER(vp)]
@@ -750,6 +759,43 @@ def fetch_ragged_plan_info(inbuf: int, inoutbuf: int, inout_displs, fetchbuf: in
         raise LookupError(f"MPIR_Hip_fetch_ragged_plan_info: {rc}")
     return dict(zip(("form", "launches", "groups", "per", "rounds", "lds_entries", "packed_sides_aligned"),
                     (int(v) for v in out)))
+
+
+# ---- fetching ordered indexed reductions (MPIX_Reduce_local_fetch_indexed_ordered)
+def reduce_local_fetch_indexed_ordered(inbuf: int, in_displs, inoutbuf: int, inout_displs, fetchbuf: int, order,
+                                       disp_unit: int, nblocks: int, blocklen: int, datatype: int, op: int,
+                                       stream: int = 0) -> int:
+    """MPIX_Reduce_local_fetch_indexed_ordered: reduce_local_indexed_ordered that
+    also hands out, in block k of the packed fetchbuf, the bytes block k's target
+    held after contributions 0 .. k - 1 and before contribution k (reduce_local_fetch
+    block by block in table order).  MPI_NO_OP (inbuf and in_displs may be 0 / None)
+    and MPI_REPLACE are accepted.  order: as for reduce_local_indexed_ordered, or
+    None with inout_displs given: equal entries of inout_displs are adjacent (in
+    particular: no repeats).  Both tables None: reduce_local_fetch on nblocks *
+    blocklen elements.  Tables and stream as for reduce_local_indexed_ordered."""
+    return load().MPIX_Reduce_local_fetch_indexed_ordered(
+        ctypes.c_void_p(inbuf or None), ctypes.c_void_p(_table_addr(in_displs) or None), ctypes.c_void_p(inoutbuf or None),
+        ctypes.c_void_p(_table_addr(inout_displs) or None), ctypes.c_void_p(fetchbuf or None),
+        ctypes.c_void_p(_order_addr(order) or None), disp_unit, nblocks, blocklen, datatype, op,
+        ctypes.c_void_p(stream or None))
+
+
+def fetch_indexed_ordered_plan_info(inbuf: int, in_displs, inoutbuf: int, inout_displs, fetchbuf: int, order,
+                                    disp_unit: int, nblocks: int, blocklen: int, datatype: int, op: int) -> dict:
+    """MPIR_Hip_fetch_indexed_ordered_plan_info: indexed_ordered_plan_info's outputs
+    for the launches of the fetching ordered call (fetchbuf joins the vector
+    form's alignment test; the tables are only compared with 0).  Raises as
+    indexed_plan_info does."""
+    out = (ctypes.c_uint64 * 6)()
+    rc = load().MPIR_Hip_fetch_indexed_ordered_plan_info(
+        ctypes.c_void_p(inbuf or None), ctypes.c_void_p(_table_addr(in_displs) or None), ctypes.c_void_p(inoutbuf or None),
+        ctypes.c_void_p(_table_addr(inout_displs) or None), ctypes.c_void_p(fetchbuf or None),
+        ctypes.c_void_p(_order_addr(order) or None), disp_unit, nblocks, blocklen, op & 0xFF, _ELEM_BY_HANDLE[datatype], out)
+    if rc == MPIR_HIP_EARG:
+        raise ValueError("MPIR_Hip_fetch_indexed_ordered_plan_info: arguments refused")
+    if rc:
+        raise LookupError(f"MPIR_Hip_fetch_indexed_ordered_plan_info: {rc}")
+    return dict(zip(("form", "launches", "groups", "per", "threshold", "rows_per_launch"), (int(v) for v in out)))
 
 
 MPIX_HIP_ALG_AUTO = 0
