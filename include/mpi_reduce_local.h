@@ -765,6 +765,100 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_fetch_indexed_ordered(const void *inbuf, 
                              void *inoutbuf, const MPI_Aint * inout_displs, void *fetchbuf, const int *order,
                              MPI_Aint disp_unit, int nblocks, int blocklen,
                              MPI_Datatype datatype, MPI_Op op, void *hip_stream);
+/* Ordered compare-and-swap: many MPI_Compare_and_swap targets in one call, in
+ * table order -- the one RMA atomic that is not an MPI_Op, so no MPIX_Reduce_local
+ * call expresses it (MPI_REPLACE through the fetching ordered call swaps
+ * unconditionally).  The reference's target handlers copy the old value out, call
+ * MPIR_Compare_equal and, where it is true, copy the origin value in, under the
+ * window lock (src/mpid/ch3/src/ch3u_rma_pkthandler.c:1166-1178,
+ * ch3u_handle_recv_req.c:1677, src/mpid/ch3/include/mpid_rma_shm.h:625-632).
+ * This call is the CASes a target has queued, a deterministic lock or slot
+ * claim, a hash-table insert whose winner is the earliest table position
+ * instead of whoever wins an atomic's race.
+ * count entries of ONE element each (MPI_Compare_and_swap has no count, so
+ * there is no blocklen).  origin, compare and result are packed by entry number;
+ * entry k's target is (char *) target + target_displs[k] * disp_unit, signed
+ * displacements as in the indexed calls.  The call is exactly
+ *   for k = 0 .. count - 1, one after another in that order:
+ *     result[k] receives the bytes the target holds (a byte copy);
+ *     if MPIR_Compare_equal(&compare[k], target_k, datatype): target_k receives
+ *         the bytes of origin[k].
+ * result[k] is what the target held after entries 0 .. k - 1 and before entry k;
+ * a successful swap makes a later compare against the new value succeed, a failed
+ * one leaves the value for the next entry.  No byte outside the targets, outside
+ * result[0, count x size), or in any table is written.
+ *   One value: a run of entries on one target is folded by one lane, the target
+ *       loaded once into a register that is handed to result before every step.
+ *       The target is stored once at the end of a run, and only when some entry
+ *       of the run swapped (a run of failed compares writes no target byte;
+ *       nothing can observe the difference from storing the unchanged value).
+ *   Types: exactly MPIR_Type_is_rma_atomic (src/mpi/rma/rmatypeutil.c:23-43) for
+ *       this build -- the C integer group (mpir_op_util.h:263-281), MPI_CHAR,
+ *       MPI_AINT, MPI_OFFSET, MPI_COUNT, MPI_C_BOOL and MPI_BYTE.  Every other
+ *       basic or pair type (MPI_WCHAR, the floating, complex and pair types,
+ *       MPIX_C_FLOAT16) is MPI_ERR_TYPE, "Datatype (...) not permitted for atomic
+ *       operations" (errnames.txt:206-207); a null or invalid handle is
+ *       MPI_ERR_TYPE.  For every accepted type MPIR_Compare_equal
+ *       (rmatypeutil.c:53-76) is `==` on an integer type, _Bool or unsigned char,
+ *       which is equality of the element's bytes (_Bool is compared as its byte,
+ *       as this library treats it everywhere; MPI_BYTE as unsigned char,
+ *       rmatypeutil.c:65 -- of the validity test's groups the compare leaves out
+ *       BYTE_EXTRA alone, which is empty, mpir_op_util.h:346).  The kernels
+ *       therefore go by the element's size, 1, 2, 4 or 8 bytes, not by type.
+ *   order: MPIX_Reduce_local_order's table under
+ *       MPIX_Reduce_local_indexed_ordered's rules, unchanged.  order NULL with
+ *       target_displs given promises that equal entries are adjacent (a host
+ *       table is held to it, as in MPIX_Reduce_local_fetch_indexed_ordered).
+ *       target_displs NULL is a contiguous target, element k entry k: no entry
+ *       repeats, and order given then is MPI_ERR_ARG.
+ *   Arguments, in this order: count < 0 MPI_ERR_COUNT; the datatype; disp_unit
+ *       <= 0 MPI_ERR_ARG; count 0 succeeds and looks at no pointer or table; NULL
+ *       origin, compare or result MPI_ERR_ARG (MPIR_ERRTEST_ARGNULL,
+ *       src/mpi/rma/compare_and_swap.c:115-117); MPI_IN_PLACE for any of the four
+ *       buffers MPI_ERR_BUFFER; origin == target or compare == target
+ *       MPI_ERR_BUFFER under MPIR_CVAR_COLL_ALIAS_CHECK; order without
+ *       target_displs MPI_ERR_ARG; result's packed range overlapping origin's,
+ *       compare's or a contiguous target's MPI_ERR_BUFFER whatever the alias
+ *       check says (origin and compare are only read and may overlap or be equal).
+ *   Residency and host tables are MPIX_Reduce_local_fetch_indexed_ordered's:
+ *       everything device memory on one device; with hip_stream NULL a table may
+ *       be host memory and gets that call's checks (displacement overflow and an
+ *       order that is no stable sort MPI_ERR_ARG, with no order the adjacency
+ *       promise; the residency of the lowest and highest target, and result
+ *       meeting ANY byte of the targets' span, MPI_ERR_BUFFER); a host table with
+ *       a stream is MPI_ERR_BUFFER.  A device order that breaks its conditions
+ *       gives an undefined result, but every index read from it is clamped: reads
+ *       stay inside the tables and stores inside result and the named targets.
+ *   A call that returns an error has written nothing.
+ *   hip_stream NULL: synchronous; otherwise enqueued on that stream without
+ *       waiting.  With device tables everything travels in the kernel arguments:
+ *       no allocation, no library scratch, so the call can be captured into a
+ *       graph on one stream.
+ *   Element access is byte-wise where it must be: any target alignment works, odd
+ *       byte displacements with disp_unit 1 included.  A contiguous target moves
+ *       as 16-byte vectors on a 16 KiB tile grid where all four pointers share
+ *       one offset mod 16 and the target is naturally aligned, else by elements.
+ *   Measured: synchronous calls, medians of alternated rounds, the rounds' medians
+ *       within 1 % of these (tools/cas_ab.py, profiles/cas/cas_ab.log; DESIGN.md,
+ *       Ordered compare-and-swap, has the tables); values from three words, a third
+ *       of the compares succeeding.  Against the unconditional swap a caller had
+ *       before, MPIX_Reduce_local_fetch_indexed_ordered with MPI_REPLACE and
+ *       blocklen 1 on the same tables (by the bytes per entry this call moves at
+ *       most 5 : 4 of it): 65,536 entries of MPI_LONG in 16.8 against 21.1 us with
+ *       no repeats, 20.1 against 27.7 at 4 entries per target, 89 against 182 at
+ *       64; MPI_INT 18.3 against 30.5, 20.8 against 42.6, 84 against 328.  Every
+ *       entry on one target, the serial worst case: 13.0 ms (0.2 us an entry)
+ *       against 14.7.  Walking a run four positions at a time against one at a
+ *       time (the same sources built both ways, alternated): 20.1 against 21.3 us
+ *       at 4 per target, 89 against 115 at 64, 13.0 against 17.5 ms on one target,
+ *       equal with no repeats.  A contiguous MPI_LONG target against
+ *       MPIX_Reduce_local_fetch with MPI_BXOR, four streams where this call moves
+ *       five: 10.4 against 9.9 us at 16 KiB, 222 against 191 us at 256 MiB (1.17 x,
+ *       byte bound 1.25; the five streams over the whole call's time are 0.755 of
+ *       the 8 TB/s peak; the kernel alone was not measured). */
+MPICH_API_PUBLIC int MPIX_Compare_and_swap_indexed_ordered(const void *origin, const void *compare,
+                             void *target, const MPI_Aint * target_displs, void *result, const int *order,
+                             MPI_Aint disp_unit, int count, MPI_Datatype datatype, void *hip_stream);
 MPICH_API_PUBLIC int MPIX_Reduce_local_set_errhandler(MPI_Errhandler errhandler);
 MPICH_API_PUBLIC int MPIX_Reduce_local_get_errhandler(MPI_Errhandler * errhandler);
 

@@ -533,6 +533,51 @@ int MPIR_Hip_fetch_indexed_ordered_plan_info(const void *inbuf, const int64_t *i
                                              uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen, int op, int elem,
                                              uint64_t out[6]);
 
+/* Ordered compare-and-swap: `count` entries of ONE element each, the target side of
+ * MPI_Compare_and_swap many times over.  origin, compare and result are packed
+ * by entry number; entry k's target is target + displs[k] * disp_unit bytes
+ * (signed displacements).  For k = 0 .. count - 1 in that order: result[k]
+ * receives the bytes the target holds (a byte copy), and where those bytes equal
+ * compare[k]'s the target receives origin[k]'s.  Equality is equality of the
+ * element's bytes, so the kernels (k_cas_indexed_ordered, k_cas_contig;
+ * reduce_kernels.hpp) are chosen by the element class's SIZE, 1, 2, 4 or 8 bytes
+ * (any other class: MPIR_HIP_ENOKERNEL).  One register value per run of equal
+ * displacements: loaded from the target once, handed to result before every
+ * step, stored back once if some step swapped.
+ * Tables: `order` as for MPIR_Hip_reduce_fetch_indexed_ordered -- the ordered
+ * call's table, or NULL with displs given for the caller's promise that equal
+ * entries of displs are adjacent (a host displs is held to it).  displs NULL: a
+ * contiguous target, element k is entry k (order given then: MPIR_HIP_EARG).
+ * The argument checks are that call's in its order (disp_unit, a count of 0
+ * succeeds looking at no pointer, count > INT32_MAX), as are residency (all four
+ * buffers device memory on one device, the first and last byte of each packed
+ * one), host tables (a synchronous call on the library stream only; overflow of
+ * displs[k] * disp_unit and an invalid order MPIR_HIP_EARG; result meeting any
+ * byte from the lowest target's first to the highest target's last
+ * MPIR_HIP_EBUFFER) and the clamping of every index read from a device order.
+ * A call that fails has written nothing.  With device tables everything travels
+ * in the kernel arguments (no allocation, no library buffer: graph-capturable). */
+#define MPIR_HIP_CAS_EMPTY        0   /* count == 0: nothing to do */
+#define MPIR_HIP_CAS_CONTIG_TILE  1   /* no table; the four pointers at one offset mod 16, the target naturally aligned: the 16 KiB tile grid */
+#define MPIR_HIP_CAS_CONTIG_ELEMS 2   /* no table, any other alignment: element runs */
+#define MPIR_HIP_CAS_INDEXED      3   /* a displacement table: one lane per sorted position */
+int MPIR_Hip_cas_indexed_ordered(const void *origin, const void *compare, void *target, const int64_t *displs,
+                                 void *result, const int *order, uint64_t disp_unit, uint64_t count, int elem,
+                                 void *hip_stream, int sync);
+
+/* For tests and tools: the launches MPIR_Hip_cas_indexed_ordered would make for
+ * device operands at these addresses (never dereferenced, the tables only
+ * compared with NULL; no GPU needed).  out[0] the form (MPIR_HIP_CAS_*), out[1]
+ * launches, out[2] workgroups over the whole call, out[3] rows_per_launch (sorted
+ * positions of a full launch; MPIR_Hip_strided_test_max_groups lowers the
+ * per-launch workgroup cap behind it), out[4] the entries one workgroup owns,
+ * out[5] kCasAhead (the positions a run is walked at a time), out[6] / out[7]
+ * the head and tail elements workgroup 0 of the tile form takes.  Returns as the
+ * call does, residency and the tables' contents apart. */
+int MPIR_Hip_cas_plan_info(const void *origin, const void *compare, const void *target, const int64_t *displs,
+                           const void *result, const int *order, uint64_t disp_unit, uint64_t count, int elem,
+                           uint64_t out[8]);
+
 /* Flags for the calling thread's later MPIR_Hip_combine calls; returns the
  * previous flags.  MPIR_HIP_COMBINE_UNCAPPED: the fused folds run without the
  * LDS reservation that caps a CU at one (P >= 5) or three (P = 3, 4) of their

@@ -41,6 +41,7 @@ FetchRaggedEntry g_fetch_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchRaggedEntry g_fetch_ragged_bytes[2][kFetchRaggedSizes];
 FetchOrderedEntry g_fetch_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchOrderedEntry g_fetch_ordered_bytes[2][kFetchRaggedSizes];
+CasEntry g_cas[kCasSizes];
 
 // Strided rows of at least this many bytes take the wide form (one row's tiles
 // per G workgroups), shorter ones the narrow form (rows flattened into units):
@@ -1014,6 +1015,38 @@ int fetch_ordered_host_adjacent(const int64_t *io_displs, uint64_t nblocks) {
     for (uint64_t p = 1; p < nblocks; ++p)
         if (io_displs[idx[p - 1]] == io_displs[idx[p]] && idx[p] != idx[p - 1] + 1) return MPIR_HIP_EARG;
     return MPIR_HIP_OK;
+}
+
+// ---- ordered compare-and-swap.  The kernels of an element class: those of its
+// size, 1 to 8 bytes (null: none)
+const CasEntry *cas_kernels(int elem) {
+    if (elem <= 0 || elem >= MPIR_HIP_NELEMS) return nullptr;
+    const uint64_t esz = g_elem_size[elem];
+    int l = 0;
+    while (l < kCasSizes && ((uint64_t)1 << l) != esz) ++l;
+    return l < kCasSizes && g_cas[l].launch && g_cas[l].contig && g_cas[l].plan ? &g_cas[l] : nullptr;
+}
+
+// the argument checks MPIR_Hip_cas_indexed_ordered makes before it looks at a
+// pointer, in the fetching ordered call's order.  MPIR_HIP_OK with *form EMPTY,
+// INDEXED, or CONTIG_ELEMS for a call with no table (the plan then says which of
+// the contiguous kernel's two paths).
+int cas_args(const void *displs, const void *order, uint64_t disp_unit, uint64_t count, int elem, int *form) {
+    if (!cas_kernels(elem)) return MPIR_HIP_ENOKERNEL;
+    if (!disp_unit || disp_unit > (~(uint64_t)0 >> 1)) return MPIR_HIP_EARG;
+    *form = MPIR_HIP_CAS_EMPTY;
+    if (!count) return MPIR_HIP_OK;
+    if (count > (uint64_t)INT32_MAX) return MPIR_HIP_EARG;
+    if (!displs && order) return MPIR_HIP_EARG;             // a contiguous target has no repeats to order
+    *form = displs ? MPIR_HIP_CAS_INDEXED : MPIR_HIP_CAS_CONTIG_ELEMS;
+    return MPIR_HIP_OK;
+}
+
+// sorted positions of one launch of the indexed form: whole workgroups up to the
+// per-launch cap (MPIR_Hip_strided_test_max_groups lowers it)
+uint64_t cas_rows_per_launch(uint64_t count) {
+    const uint64_t cap = t_strided_cap && t_strided_cap < kBatchMaxGroups ? t_strided_cap : kBatchMaxGroups;
+    return std::min(cap * kCasPerGroup, count);
 }
 
 }  // namespace
@@ -2217,6 +2250,148 @@ int MPIR_Hip_reduce_fetch_indexed_ordered(const void *inbuf, const int64_t *in_d
     // (launches made before one that failed are still queued on the library stream)
     if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
     if (e != hipSuccess) rc = set_err(e, "fetching ordered indexed launch");
+    else if (sync) rc = wait_stream(dev, s);
+    return rc;
+}
+
+int MPIR_Hip_cas_plan_info(const void *origin, const void *compare, const void *target, const int64_t *displs,
+                           const void *result, const int *order, uint64_t disp_unit, uint64_t count, int elem,
+                           uint64_t out[8]) {
+    int form = 0;
+    const int rc = cas_args(displs, order, disp_unit, count, elem, &form);
+    if (rc != MPIR_HIP_OK) return rc;
+    for (int k = 0; k < 8; ++k) out[k] = 0;
+    out[0] = (uint64_t)form;
+    out[5] = (uint64_t)kCasAhead;
+    if (form == MPIR_HIP_CAS_EMPTY) return MPIR_HIP_OK;
+    if (form == MPIR_HIP_CAS_INDEXED) {
+        const uint64_t rpl = cas_rows_per_launch(count);
+        out[1] = (count + rpl - 1) / rpl;
+        // (a launch's positions are whole workgroups but the last launch's)
+        out[2] = (count / rpl) * ((rpl + kCasPerGroup - 1) / kCasPerGroup) + (count % rpl + kCasPerGroup - 1) / kCasPerGroup;
+        out[3] = rpl;
+        out[4] = kCasPerGroup;
+        return MPIR_HIP_OK;
+    }
+    const CasContigArgs a{static_cast<const char *>(origin), static_cast<const char *>(compare),
+                          static_cast<char *>(const_cast<void *>(target)), static_cast<char *>(const_cast<void *>(result)),
+                          count};
+    FetchPlan p;
+    cas_kernels(elem)->plan(&a, &p);
+    out[0] = p.tile ? MPIR_HIP_CAS_CONTIG_TILE : MPIR_HIP_CAS_CONTIG_ELEMS;
+    out[1] = 1;
+    out[2] = p.groups;
+    out[3] = count;
+    out[4] = kTileBytes / g_elem_size[elem];
+    out[6] = p.nhead;
+    out[7] = p.ntail;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_cas_indexed_ordered(const void *origin, const void *compare, void *target, const int64_t *displs,
+                                 void *result, const int *order, uint64_t disp_unit, uint64_t count, int elem,
+                                 void *hip_stream, int sync) {
+    int form = 0;
+    int rc = cas_args(displs, order, disp_unit, count, elem, &form);
+    if (rc != MPIR_HIP_OK || form == MPIR_HIP_CAS_EMPTY) return rc;
+    ctx().err[0] = 0;
+    const CasEntry &en = *cas_kernels(elem);
+    // Everything classified before anything is enqueued, as the fetching ordered
+    // call classifies: the four bases, the last byte of the three packed buffers
+    // and of a contiguous target, then the two tables -- device memory on the
+    // operands' device or, in a synchronous call on the library stream, host
+    // memory, which is then read and checked.  A host displacement table also
+    // gives the targets' extent, which result must not meet, and beside no order
+    // table is held to the promise that equal entries are adjacent.
+    const uint64_t esz = g_elem_size[elem];
+    const uint64_t bytes = count * esz;
+    const char *base[4] = {static_cast<const char *>(origin), static_cast<const char *>(compare),
+                           static_cast<char *>(result), static_cast<char *>(target)};
+    const void *table[2] = {displs, order};
+    const size_t tbytes[2] = {(size_t)count * sizeof(int64_t), (size_t)count * sizeof(int)};
+    bool host_table[2] = {false, false};
+    int dev = -1;
+    DeviceSpan span[4];
+    for (int k = 0; k < 4; ++k) {
+        int d = -1;
+        if (classify_in_span(base[k], &d, span[k]) != LOC_DEVICE || (dev >= 0 && d != dev)) return MPIR_HIP_EBUFFER;
+        dev = d;
+        if ((k < 3 || !displs) && (classify_in_span(base[k] + (bytes - 1), &d, span[k]) != LOC_DEVICE || d != dev))
+            return MPIR_HIP_EBUFFER;
+    }
+    for (int k = 0; k < 2; ++k) {
+        if (!table[k]) continue;
+        if (table_on_device(table[k], tbytes[k], &dev, &rc)) {
+            if (rc != MPIR_HIP_OK) return rc;
+            continue;
+        }
+        if (hip_stream || !sync) return MPIR_HIP_EBUFFER;       // a host table would be read after the call returned
+        host_table[k] = true;
+        if (k == 0) {
+            const char *first = nullptr, *last = nullptr;
+            rc = indexed_host_table(base[3], displs, disp_unit, count, esz, dev, &first, &last);
+            if (rc != MPIR_HIP_OK) return rc;
+            // the old values must not land on a target: anywhere in the targets' extent is refused
+            const uintptr_t r0 = reinterpret_cast<uintptr_t>(result), r1 = r0 + (bytes - 1);
+            if (r0 <= reinterpret_cast<uintptr_t>(last) && reinterpret_cast<uintptr_t>(first) <= r1) return MPIR_HIP_EBUFFER;
+            if (!order) rc = fetch_ordered_host_adjacent(displs, count);
+        } else {
+            rc = ordered_host_order(order, host_table[0] ? displs : nullptr, count);
+        }
+        if (rc != MPIR_HIP_OK) return rc;
+    }
+    const CasContigArgs ca{base[0], base[1], static_cast<char *>(target), static_cast<char *>(result), count};
+    if (form != MPIR_HIP_CAS_INDEXED) {
+        FetchPlan p;
+        en.plan(&ca, &p);
+        if (p.groups > kBatchMaxGroups) {
+            snprintf(ctx().err, sizeof(ctx().err), "a compare-and-swap of this size needs more workgroups than one launch holds");
+            return MPIR_HIP_ERUNTIME;
+        }
+    }
+    DeviceScope on(dev);
+    if (!on.ok()) return on.err();
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (!s) rc = get_stream(dev, S_MAIN, &s);
+    if (rc != MPIR_HIP_OK) return rc;
+    if (host_table[0] || host_table[1]) {
+        // host tables into the thread's table buffer, stream-ordered ahead of the
+        // kernels; the order table's ints last, so the displacements stay 8-byte aligned
+        size_t total = 0;
+        for (int k = 0; k < 2; ++k) total += host_table[k] ? tbytes[k] : 0;
+        char *buf = nullptr;
+        rc = get_tables(dev, total, &buf);
+        if (rc != MPIR_HIP_OK) return rc;               // (nothing of this call is queued yet)
+        for (int k = 0; k < 2; ++k) {
+            if (!host_table[k]) continue;
+            const hipError_t ce = hipMemcpyAsync(buf, table[k], tbytes[k], hipMemcpyHostToDevice, s);
+            if (ce != hipSuccess) {
+                // (the other table's copy may be queued on the library stream)
+                ctx().dev[dev].main_pending = true;
+                return set_err(ce, "compare-and-swap table copy");
+            }
+            table[k] = buf;
+            buf += tbytes[k];
+        }
+    }
+    hipError_t e = hipSuccess;
+    if (form == MPIR_HIP_CAS_INDEXED) {
+        // later ranges of sorted positions; the bases and the tables are the call's in
+        // every launch (a head test looks back and a run goes on across a launch boundary)
+        const uint64_t rpl = cas_rows_per_launch(count);
+        for (uint64_t pos0 = 0; pos0 < count && e == hipSuccess; pos0 += rpl) {
+            const uint64_t n = std::min(rpl, count - pos0);
+            const CasArgs a{base[0], base[1], static_cast<char *>(target), static_cast<const int64_t *>(table[0]),
+                            static_cast<char *>(result), static_cast<const int *>(table[1]), disp_unit, (uint32_t)count,
+                            (uint32_t)pos0, (uint32_t)n, 0};
+            e = en.launch(&a, (n + kCasPerGroup - 1) / kCasPerGroup, s);
+        }
+    } else {
+        e = en.contig(&ca, s);
+    }
+    // (launches made before one that failed are still queued on the library stream)
+    if (!hip_stream && (!sync || e != hipSuccess)) ctx().dev[dev].main_pending = true;
+    if (e != hipSuccess) rc = set_err(e, "compare-and-swap launch");
     else if (sync) rc = wait_stream(dev, s);
     return rc;
 }

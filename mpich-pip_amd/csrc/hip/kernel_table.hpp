@@ -41,6 +41,9 @@ typedef hipError_t (*ragged_fn)(const RaggedArgs *, hipStream_t);
 typedef void (*fplan_fn)(const FetchArgs *, FetchPlan *);
 typedef hipError_t (*fetch_ragged_fn)(const FetchRaggedArgs *, hipStream_t);
 typedef hipError_t (*fetch_ordered_fn)(const FetchOrderedArgs *, uint64_t, hipStream_t);
+typedef hipError_t (*cas_fn)(const CasArgs *, uint64_t, hipStream_t);
+typedef hipError_t (*cas_contig_fn)(const CasContigArgs *, hipStream_t);
+typedef void (*cas_plan_fn)(const CasContigArgs *, FetchPlan *);
 
 // plan: plan_reduce<T> (reduce_kernels.hpp) for the classes whose launcher is
 // launch_reduce -- the kernel, grid and argument bytes the direct AQL dispatch
@@ -95,6 +98,14 @@ constexpr int kFetchRaggedSizes = 6;
 // g_fetch_ordered_bytes[which][log2 size]: the same kernel over the two byte
 // functors, laid out as g_fetch_ragged_bytes is (reg_fetch_ordered_bytes.hip).
 struct FetchOrderedEntry { fetch_ordered_fn launch; };
+// g_cas[log2 size]: the ordered compare-and-swap kernels of one element size, 1 to
+// 8 bytes (MPIR_Hip_cas_indexed_ordered; reg_cas.hip): launch =
+// launch_cas_indexed_ordered<N>, one launch of k_cas_indexed_ordered over a range
+// of sorted positions; contig = launch_cas_contig<N>, the one launch of
+// k_cas_contig for a call with no table; plan = cas_plan<N>, the plan that launch
+// makes, for MPIR_Hip_cas_plan_info.
+struct CasEntry { cas_fn launch; cas_contig_fn contig; cas_plan_fn plan; };
+constexpr int kCasSizes = 4;
 
 // float / double SUM and PROD on the host: the SSE instruction itself.  The
 // reference's loop `a[i] = a[i] + b[i]` (opsum.c:21-76, gcc -O2) is an
@@ -172,6 +183,7 @@ extern FetchRaggedEntry g_fetch_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchRaggedEntry g_fetch_ragged_bytes[2][kFetchRaggedSizes];
 extern FetchOrderedEntry g_fetch_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchOrderedEntry g_fetch_ordered_bytes[2][kFetchRaggedSizes];
+extern CasEntry g_cas[kCasSizes];
 constexpr int kMultiMaxP = 8;
 extern multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 
@@ -245,6 +257,12 @@ void reg_fetch_ordered_bytes() {
     static_assert(LOG2 >= 0 && LOG2 < kFetchRaggedSizes, "element sizes 1 to 32 bytes");
     g_fetch_ordered_bytes[0][LOG2] = FetchOrderedEntry{&launch_fetch_indexed_ordered<OpFetchNoOp, RawBytes<(1 << LOG2)>>};
     g_fetch_ordered_bytes[1][LOG2] = FetchOrderedEntry{&launch_fetch_indexed_ordered<OpFetchSwap, RawBytes<(1 << LOG2)>>};
+}
+// the ordered compare-and-swap kernels of elements of 1 << LOG2 bytes, from reg_cas.hip
+template <int LOG2>
+void reg_cas() {
+    static_assert(LOG2 >= 0 && LOG2 < kCasSizes, "element sizes 1 to 8 bytes");
+    g_cas[LOG2] = CasEntry{&launch_cas_indexed_ordered<(1 << LOG2)>, &launch_cas_contig<(1 << LOG2)>, &cas_plan<(1 << LOG2)>};
 }
 template <class Op, class T>
 void reg_multi(int op, int elem) {

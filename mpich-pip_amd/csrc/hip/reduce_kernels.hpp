@@ -2604,4 +2604,309 @@ hipError_t launch_combine_p(const void *const *ins, void *out_, uint64_t count, 
     return launch_combine_pu<Op, T, P, TREE, (P >= 5 ? 1 : 4), (P >= 5 ? 1024 : kThreads)>(ins, out_, count, s);
 }
 
+// ============================================================================
+// Ordered compare-and-swap (MPIR_Hip_cas_indexed_ordered): `count` entries of
+// ONE element each, the target side of MPI_Compare_and_swap many times over --
+// the reference's handlers copy the old value out, call MPIR_Compare_equal and,
+// where it is true, copy the origin value in, under the window lock
+// (ch3u_rma_pkthandler.c:1166-1178, ch3u_handle_recv_req.c:1677,
+// mpid_rma_shm.h:625-632).  origin, compare and result are packed by entry
+// number; entry k's target is target + displs[k] * disp_unit.  For k = 0 ..
+// count - 1 in that order:
+//     result[k] = the bytes target_k holds;  if they equal compare[k]: target_k = origin[k]
+// Equality is equality of the element's N bytes (every type MPIR_Compare_equal
+// accepts is an integer, _Bool or a byte), so the kernels are per element SIZE
+// over RawBytes<N>, N = 1, 2, 4, 8, never per type.
+//
+// k_cas_indexed_ordered<N>: one lane per sorted position, kCasPerGroup
+// positions a workgroup (a lane's kCasPerLane positions a wave apart, their
+// order and displacement loads issued in straight runs).
+//   * Head test, clamping of every index read from a device `order`, and the
+//     pos0 / nrows / count launch split are reduce_ordered_narrow's: position p
+//     heads a run iff p == 0 or displs[order[p - 1]] != displs[order[p]]; a
+//     run belongs entirely to its head, across workgroup and launch boundaries;
+//     a null `order` is the identity.  Non-heads load two entries of each table
+//     and nothing else.
+//   * The head loads the target element ONCE into a register.  For each entry of
+//     the run it stores the register to result[k] (nt), and where the register
+//     equals compare[k] takes origin[k].  It stores the target once at the end
+//     of the run, and only if some entry of the run swapped (a run of failed
+//     compares writes no target byte; nothing can observe the difference).
+//   * The run is walked kCasAhead positions at a time: the order entries of the
+//     next positions load together, then their displacements, compare values
+//     and origin values together (all three depend on the order entry alone),
+//     and the selects follow in order -- two dependent round trips per
+//     kCasAhead entries where an element-at-a-time loop pays three per entry.
+//   * Every element access is memcpy-style: any target alignment works (odd byte
+//     displacements with disp_unit 1), and unaligned packed bases.
+// No LDS, no scratch, no gridDim.  72 bytes of kernel arguments.
+//
+// k_cas_contig<N> (displs null: element k is entry k, no entry repeats):
+// k_reduce_fetch's structure with two more streams.  The 16 KiB tile grid sits
+// on the target's address; the tile path is taken only where origin, compare
+// and result all share the target's offset mod 16 and the target is naturally
+// aligned (cas_split: fetch_split extended to the fourth pointer).  A lane loads
+// the target, compare and origin vectors, stores the target vector to result and
+// a per-element blend to the target; tile 0 takes the head and tail elements.
+// Every other alignment: the element form, workgroup g owning elements [g, g +
+// 1) x kTileBytes / N.  cas_split / batch_seg_groups are the one source of the
+// split and the workgroup count for the planner (cas_plan) and the kernel.
+// 256 threads, 40 bytes of kernel arguments, no LDS, no scratch, no gridDim.
+// All stores nt.
+// ============================================================================
+// (a build-time override for tools/cas_ab.py's look-ahead comparison only)
+#ifndef MPIR_CAS_AHEAD
+#define MPIR_CAS_AHEAD 4
+#endif
+constexpr int kCasAhead = MPIR_CAS_AHEAD;
+constexpr int kCasPerLane = 4;
+constexpr uint32_t kCasPerGroup = kThreads * kCasPerLane;
+static_assert(kCasAhead >= 1 && kCasAhead <= 8, "positions looked ahead of a run's current end");
+
+struct CasArgs {
+    const char *origin;         // packed: entry k at k * N
+    const char *compare;        // packed
+    char *target;
+    const int64_t *displs;      // never null
+    char *result;               // packed
+    const int *order;           // sorted position -> entry number; null: the identity
+    uint64_t disp_unit;         // bytes per displacement unit, > 0
+    uint32_t count;             // entries of the whole call
+    uint32_t pos0;              // this launch's first sorted position
+    uint32_t nrows;             // sorted positions of this launch, > 0
+    uint32_t pad_;
+};
+
+struct CasContigArgs {
+    const char *origin;
+    const char *compare;
+    char *target;
+    char *result;
+    uint64_t count;             // elements, > 0
+};
+
+template <int N>
+__device__ __forceinline__ bool cas_equal(const RawBytes<N> &x, const RawBytes<N> &y) {
+    if constexpr (N == 8) return x.v[0] == y.v[0] && x.v[1] == y.v[1];     // all 64 bits
+    else return x.v == y.v;
+}
+
+// the entry at sorted position p (p < count), clamped into the tables
+__device__ __forceinline__ uint32_t cas_entry(const CasArgs &a, uint32_t p) {
+    if (!a.order) return p;                                 // (uniform: a kernel argument)
+    const uint32_t k = (uint32_t)a.order[p];
+    return k < a.count ? k : a.count - 1;
+}
+
+template <int N>
+__global__ __launch_bounds__(kThreads) void k_cas_indexed_ordered(CasArgs a) {
+    typedef RawBytes<N> Raw;
+    const unsigned t = threadIdx.x;
+    const uint64_t r0 = (uint64_t)blockIdx.x * kCasPerGroup;
+    // a position past the launch's last is clamped into it: its table loads need no branch
+    const uint64_t last = a.nrows - 1;
+    uint32_t pos[kCasPerLane], k[kCasPerLane], kp[kCasPerLane], kn[kCasPerLane];
+    int64_t d[kCasPerLane], dp[kCasPerLane], dn[kCasPerLane];
+    bool head[kCasPerLane];
+#pragma unroll
+    for (int j = 0; j < kCasPerLane; ++j) {
+        const uint64_t r = r0 + t + (uint64_t)j * kThreads;
+        head[j] = r <= last;
+        pos[j] = a.pos0 + (uint32_t)(head[j] ? r : last);
+    }
+#pragma unroll
+    for (int j = 0; j < kCasPerLane; ++j) k[j] = cas_entry(a, pos[j]);
+#pragma unroll
+    for (int j = 0; j < kCasPerLane; ++j) kp[j] = cas_entry(a, pos[j] ? pos[j] - 1 : 0);
+    // (the position after, with the same loads: a run of one ends without another round trip)
+#pragma unroll
+    for (int j = 0; j < kCasPerLane; ++j) kn[j] = cas_entry(a, pos[j] + 1 < a.count ? pos[j] + 1 : pos[j]);
+#pragma unroll
+    for (int j = 0; j < kCasPerLane; ++j) d[j] = a.displs[k[j]];
+#pragma unroll
+    for (int j = 0; j < kCasPerLane; ++j) dp[j] = a.displs[kp[j]];
+#pragma unroll
+    for (int j = 0; j < kCasPerLane; ++j) dn[j] = a.displs[kn[j]];
+#pragma unroll
+    for (int j = 0; j < kCasPerLane; ++j) head[j] = head[j] && (pos[j] == 0 || d[j] != dp[j]);
+    // only heads touch data: the target's element once, and their own entry's two values
+    Raw x[kCasPerLane], c[kCasPerLane], o[kCasPerLane];
+#pragma unroll
+    for (int j = 0; j < kCasPerLane; ++j) {
+        if (!head[j]) continue;
+        __builtin_memcpy(&x[j], a.target + (uint64_t)d[j] * a.disp_unit, N);
+        __builtin_memcpy(&c[j], a.compare + (uint64_t)k[j] * N, N);
+        __builtin_memcpy(&o[j], a.origin + (uint64_t)k[j] * N, N);
+    }
+#pragma unroll
+    for (int j = 0; j < kCasPerLane; ++j) {
+        if (!head[j]) continue;
+        Raw v = x[j];
+        ordered_fetch_store(a.result + (uint64_t)k[j] * N, v);
+        bool swapped = cas_equal<N>(v, c[j]);
+        if (swapped) v = o[j];
+        bool more = dn[j] == d[j];
+        for (uint32_t q = pos[j] + 1; more && q < a.count; q += kCasAhead) {
+            uint32_t kq[kCasAhead];
+            int64_t dq[kCasAhead];
+            Raw cq[kCasAhead], oq[kCasAhead];
+            // (a position past the table is clamped into it and not counted)
+#pragma unroll
+            for (int i = 0; i < kCasAhead; ++i) kq[i] = cas_entry(a, q + i < a.count ? q + i : a.count - 1);
+#pragma unroll
+            for (int i = 0; i < kCasAhead; ++i) dq[i] = a.displs[kq[i]];
+#pragma unroll
+            for (int i = 0; i < kCasAhead; ++i) __builtin_memcpy(&cq[i], a.compare + (uint64_t)kq[i] * N, N);
+#pragma unroll
+            for (int i = 0; i < kCasAhead; ++i) __builtin_memcpy(&oq[i], a.origin + (uint64_t)kq[i] * N, N);
+#pragma unroll
+            for (int i = 0; i < kCasAhead; ++i) {
+                more = more && q + i < a.count && dq[i] == d[j];
+                if (more) {
+                    ordered_fetch_store(a.result + (uint64_t)kq[i] * N, v);
+                    if (cas_equal<N>(v, cq[i])) {
+                        v = oq[i];
+                        swapped = true;
+                    }
+                }
+            }
+        }
+        if (swapped) __builtin_memcpy(a.target + (uint64_t)d[j] * a.disp_unit, &v, N);
+    }
+}
+
+// one launch: `groups` workgroups over sorted positions [pos0, pos0 + nrows)
+template <int N>
+hipError_t launch_cas_indexed_ordered(const CasArgs *a, uint64_t groups, hipStream_t s) {
+    if (!a->nrows || !a->disp_unit || !a->displs || !a->origin || !a->compare || !a->target || !a->result ||
+        (uint64_t)a->pos0 + a->nrows > a->count || groups != (a->nrows + kCasPerGroup - 1) / kCasPerGroup ||
+        groups > kBatchMaxGroups)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_cas_indexed_ordered<N>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+// fetch_split of (origin, target, result, count), and the tile path only if
+// compare sits at the target's offset mod 16 as well
+template <int N>
+__host__ __device__ inline SegSplit cas_split(const void *origin, const void *compare, const void *target,
+                                              const void *result, uint64_t count) {
+    SegSplit s = fetch_split<RawBytes<N>>(origin, target, result, count);
+    if (s.tile && ((reinterpret_cast<uintptr_t>(compare) ^ reinterpret_cast<uintptr_t>(target)) & 15) != 0)
+        s = SegSplit{false, 0, 0, 0, 0};
+    return s;
+}
+
+// element i: the target's bytes read once, stored to result as they are, then the select
+template <int N>
+__device__ __forceinline__ void cas_elem_at(const CasContigArgs &a, uint64_t i) {
+    RawBytes<N> x, c;
+    __builtin_memcpy(&x, a.target + i * N, N);
+    __builtin_memcpy(&c, a.compare + i * N, N);
+    ordered_fetch_store(a.result + i * N, x);
+    if (cas_equal<N>(x, c)) {
+        RawBytes<N> o;
+        __builtin_memcpy(&o, a.origin + i * N, N);
+        __builtin_memcpy(a.target + i * N, &o, N);
+    }
+}
+
+// 16 bytes of N-byte elements: o's element where x's equals c's, else x's
+template <int N>
+__device__ __forceinline__ u32x4 cas_blend16(u32x4 x, u32x4 c, u32x4 o) {
+    u32x4 r;
+    if constexpr (N == 8) {
+#pragma unroll
+        for (int w = 0; w < 4; w += 2) {
+            const bool eq = x[w] == c[w] && x[w + 1] == c[w + 1];
+            r[w] = eq ? o[w] : x[w];
+            r[w + 1] = eq ? o[w + 1] : x[w + 1];
+        }
+    } else if constexpr (N == 4) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) r[w] = x[w] == c[w] ? o[w] : x[w];
+    } else {
+        constexpr uint32_t field = (1u << (8 * N)) - 1;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const uint32_t diff = x[w] ^ c[w];
+            uint32_t m = 0;
+#pragma unroll
+            for (int b = 0; b < 4 / N; ++b) m |= (diff & (field << (8 * N * b))) ? 0u : field << (8 * N * b);
+            r[w] = (o[w] & m) | (x[w] & ~m);
+        }
+    }
+    return r;
+}
+
+// reduce_fetch_tile with a fourth descriptor: tile `tile` of the grid on the
+// target's address, all four clipped alike
+template <int N>
+__device__ __forceinline__ void cas_tile(const char *origin, const char *compare, char *target, char *result,
+                                         uint64_t tile, uint64_t vbytes) {
+    const int64_t start = (int64_t)(tile * kTileBytes) - (int64_t)tile_shift(target);
+    const uint64_t lo = start > 0 ? (uint64_t)start : 0;
+    if (lo >= vbytes) return;
+    const uint64_t end = (uint64_t)(start + kTileBytes);
+    const int nrec = (int)((end < vbytes ? end : vbytes) - lo);
+    const int cut = (int)(lo - start);       // 0, or s for tile 0: lanes below it wrap out of range
+    __amdgpu_buffer_rsrc_t ror = __builtin_amdgcn_make_buffer_rsrc((void *)(origin + lo), 0, nrec, 0x00020000);
+    __amdgpu_buffer_rsrc_t rco = __builtin_amdgcn_make_buffer_rsrc((void *)(compare + lo), 0, nrec, 0x00020000);
+    __amdgpu_buffer_rsrc_t rta = __builtin_amdgcn_make_buffer_rsrc((void *)(target + lo), 0, nrec, 0x00020000);
+    __amdgpu_buffer_rsrc_t rre = __builtin_amdgcn_make_buffer_rsrc((void *)(result + lo), 0, nrec, 0x00020000);
+    const int t = (int)threadIdx.x;
+    const int wb = (t >> 6) * (kVecPerLane * 1024) + (t & 63) * 16 - cut;
+    u32x4 x[kVecPerLane], c[kVecPerLane], o[kVecPerLane];
+#pragma unroll
+    for (int u = 0; u < kVecPerLane; ++u) {
+        x[u] = __builtin_amdgcn_raw_buffer_load_b128(rta, wb + u * 1024, 0, kCachePolicyNT);
+        c[u] = __builtin_amdgcn_raw_buffer_load_b128(rco, wb + u * 1024, 0, kCachePolicyNT);
+        o[u] = __builtin_amdgcn_raw_buffer_load_b128(ror, wb + u * 1024, 0, kCachePolicyNT);
+        if (u + 1 < kVecPerLane) issue_gap();
+    }
+#pragma unroll
+    for (int u = 0; u < kVecPerLane; ++u) store16(x[u], rre, wb + u * 1024, false);
+#pragma unroll
+    for (int u = 0; u < kVecPerLane; ++u) store16(cas_blend16<N>(x[u], c[u], o[u]), rta, wb + u * 1024, false);
+}
+
+template <int N>
+__global__ __launch_bounds__(kThreads) void k_cas_contig(CasContigArgs a) {
+    const uint64_t tile = blockIdx.x;
+    const SegSplit s = cas_split<N>(a.origin, a.compare, a.target, a.result, a.count);
+    if (tile >= batch_seg_groups<RawBytes<N>>(s, a.target, a.count)) return;
+    if (s.tile) {
+        cas_tile<N>(a.origin + s.head_bytes, a.compare + s.head_bytes, a.target + s.head_bytes, a.result + s.head_bytes,
+                    tile, s.vbytes);
+        if (tile == 0) {
+            const unsigned t = threadIdx.x;
+            const uint64_t tail0 = (s.head_bytes + s.vbytes) / N;
+            if (t < s.nhead) cas_elem_at<N>(a, t);
+            else if (t >= 64 && t - 64 < s.ntail) cas_elem_at<N>(a, tail0 + (t - 64));
+        }
+        return;
+    }
+    constexpr uint64_t per = kTileBytes / N;
+    const uint64_t base = tile * per;
+    const uint64_t end = base + per < a.count ? base + per : a.count;
+    for (uint64_t i = base + threadIdx.x; i < end; i += kThreads) cas_elem_at<N>(a, i);
+}
+
+// The plan of one contiguous call: the path, the grid and tile 0's elements
+// (MPIR_Hip_cas_plan_info reports it, launch_cas_contig launches it)
+template <int N>
+void cas_plan(const CasContigArgs *a, FetchPlan *p) {
+    const SegSplit s = cas_split<N>(a->origin, a->compare, a->target, a->result, a->count);
+    *p = FetchPlan{s.tile, batch_seg_groups<RawBytes<N>>(s, a->target, a->count), s.nhead, s.ntail};
+}
+
+template <int N>
+hipError_t launch_cas_contig(const CasContigArgs *a, hipStream_t s) {
+    FetchPlan p;
+    cas_plan<N>(a, &p);
+    if (!a->count || p.groups < 1 || p.groups > kBatchMaxGroups) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_cas_contig<N>), dim3((unsigned)p.groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
 }  // namespace mpir_hip

@@ -1264,6 +1264,118 @@ static int reduce_local_fetch_indexed_ordered(const void *inbuf, const MPI_Aint 
     return MPI_SUCCESS;
 }
 
+/* ---- MPIX_Compare_and_swap_indexed_ordered: batched CAS in table order (see the header) */
+/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
+#pragma weak MPIR_Hip_cas_indexed_ordered
+#pragma weak MPIR_Hip_cas_plan_info
+static int compare_and_swap_indexed_ordered(const void *origin, const void *compare, void *target,
+                                            const MPI_Aint * target_displs, void *result, const int *order,
+                                            MPI_Aint disp_unit, int count, MPI_Datatype datatype, void *hip_stream);
+
+int MPIX_Compare_and_swap_indexed_ordered(const void *origin, const void *compare, void *target,
+                                          const MPI_Aint * target_displs, void *result, const int *order,
+                                          MPI_Aint disp_unit, int count, MPI_Datatype datatype, void *hip_stream)
+{
+    int rc;
+    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
+    rc = compare_and_swap_indexed_ordered(origin, compare, target, target_displs, result, order, disp_unit, count,
+                                          datatype, hip_stream);
+    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
+    return rc;
+}
+
+/* MPIR_Type_is_rma_atomic (src/mpi/rma/rmatypeutil.c:23-43) for a build with no
+ * Fortran and no C++: the C integer group and MPI_CHAR, MPI_AINT / MPI_OFFSET /
+ * MPI_COUNT, MPI_C_BOOL and MPI_BYTE */
+#define RMA_ATOMIC_GROUPS (G_C_INTEGER | G_C_INTEGER_EXTRA | G_FORTRAN_INTEGER | G_LOGICAL | G_BYTE)
+
+static int compare_and_swap_indexed_ordered(const void *origin, const void *compare, void *target,
+                                            const MPI_Aint * target_displs, void *result, const int *order,
+                                            MPI_Aint disp_unit, int count, MPI_Datatype datatype, void *hip_stream)
+{
+    static const char *fc = "MPIX_Compare_and_swap_indexed_ordered";
+    const MPIR_Type_desc *d;
+    const unsigned h = (unsigned) datatype;
+    uint64_t bytes;
+    int rc;
+    _Static_assert(sizeof(MPI_Aint) == sizeof(int64_t), "the shim's tables are 64-bit entries");
+    if (count < 0) {
+        MPIR_Err_set_detail("negative count %d", count);
+        return err_return(fc, MPI_ERR_COUNT);
+    }
+    /* MPIR_ERRTEST_DATATYPE, then MPIR_ERRTEST_TYPE_RMA_ATOMIC (compare_and_swap.c:119-123) */
+    d = MPIR_Type_lookup(datatype);
+    if (!d) {
+        if (datatype == MPI_DATATYPE_NULL)
+            MPIR_Err_set_detail("Null datatype");
+        else if ((h >> 30) == 1u && ((h >> 26) & 0xfu) == 0x3u)        /* another builtin-kind datatype (MPI_WCHAR) */
+            MPIR_Err_set_detail("Datatype (0x%x) not permitted for atomic operations", h);
+        else
+            MPIR_Err_set_detail("Invalid datatype");
+        return err_return(fc, MPI_ERR_TYPE);
+    }
+    if (!(d->groups & RMA_ATOMIC_GROUPS)) {
+        MPIR_Err_set_detail("Datatype (%s) not permitted for atomic operations", d->name);
+        return err_return(fc, MPI_ERR_TYPE);
+    }
+    if (disp_unit <= 0) {
+        MPIR_Err_set_detail("disp_unit %ld is not positive", (long) disp_unit);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (count == 0)     /* no pointer or table is looked at */
+        return MPI_SUCCESS;
+    /* MPIR_ERRTEST_ARGNULL (compare_and_swap.c:115-117) */
+    if (!origin || !compare || !result) {
+        MPIR_Err_set_detail("Null pointer in parameter %s", !origin ? "origin" : !compare ? "compare" : "result");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (origin == MPI_IN_PLACE || compare == MPI_IN_PLACE || target == MPI_IN_PLACE || result == MPI_IN_PLACE) {
+        MPIR_Err_set_detail("buffer '%s' cannot be MPI_IN_PLACE",
+                            origin == MPI_IN_PLACE ? "origin" : compare == MPI_IN_PLACE ? "compare" :
+                            target == MPI_IN_PLACE ? "target" : "result");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (alias_check_enabled() && (origin == target || compare == target)) {
+        MPIR_Err_set_detail("Buffers must not be aliased");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (target_displs == NULL && order != NULL) {
+        MPIR_Err_set_detail("an order table with no target_displs: a contiguous target has no repeats to order");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    bytes = (uint64_t) count *MPIR_Hip_elem_size(d->elem);
+    /* result's packed range, whatever MPIR_CVAR_COLL_ALIAS_CHECK says; origin and
+     * compare are only read and may overlap each other; a contiguous target is a range too */
+    if (ranges_overlap(result, origin, bytes) || ranges_overlap(result, compare, bytes) ||
+        (!target_displs && ranges_overlap(result, target, bytes))) {
+        MPIR_Err_set_detail("result overlaps %s", ranges_overlap(result, origin, bytes) ? "origin" :
+                            ranges_overlap(result, compare, bytes) ? "compare" : "target");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (!MPIR_Hip_cas_indexed_ordered) {
+        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_cas_indexed_ordered");
+        return err_return(fc, MPI_ERR_OTHER);
+    }
+    rc = MPIR_Hip_cas_indexed_ordered(origin, compare, target, (const int64_t *) target_displs, result, order,
+                                      (uint64_t) disp_unit, (uint64_t) count, d->elem, hip_stream, hip_stream == NULL);
+    if (rc == MPIR_HIP_EBUFFER) {
+        MPIR_Err_set_detail("%s needs device-resident buffers on one device, its tables there too (host tables: the "
+                            "synchronous call only), and result outside the targets' extent", fc);
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (rc == MPIR_HIP_EARG) {
+        MPIR_Err_set_detail("%s: a target's offset does not fit the address space, the order table is not a stable "
+                            "sort of target_displs, or with no order table equal entries of target_displs are not "
+                            "adjacent", fc);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (rc != MPIR_HIP_OK) {
+        MPIR_Op_report_hip_error(fc, rc);
+        return err_return(fc, *MPIR_Op_errno_ptr());
+    }
+    return MPI_SUCCESS;
+}
+
 /* ---- MPI_Op_create / MPI_Op_free / MPI_Op_commutative ------------------ */
 int PMPI_Op_create(MPI_User_function * user_fn, int commute, MPI_Op * op)
 {

@@ -122,6 +122,7 @@ EXPORTED_SYMBOLS = [
     "MPIX_Reduce_local_fetch_ragged", "MPIR_Hip_reduce_fetch_ragged", "MPIR_Hip_fetch_ragged_plan_info",
     "MPIX_Reduce_local_fetch_indexed_ordered", "MPIR_Hip_reduce_fetch_indexed_ordered",
     "MPIR_Hip_fetch_indexed_ordered_plan_info",
+    "MPIX_Compare_and_swap_indexed_ordered", "MPIR_Hip_cas_indexed_ordered", "MPIR_Hip_cas_plan_info",
     # device collectives (include/mpix_hip_coll.h)
     "MPIX_Hip_comm_get_unique_id", "MPIX_Hip_comm_create", "MPIX_Hip_comm_create_loopback",
     "MPIX_Hip_comm_free", "MPIX_Hip_comm_rank", "MPIX_Hip_comm_size",
@@ -246,6 +247,12 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.MPIR_Hip_fetch_indexed_ordered_plan_info.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, u64, i32, i32,
                                                              ctypes.POINTER(u64)]
     lib.MPIR_Hip_fetch_indexed_ordered_plan_info.restype = i32
+    lib.MPIX_Compare_and_swap_indexed_ordered.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_long, i32, i32, vp]
+    lib.MPIX_Compare_and_swap_indexed_ordered.restype = i32
+    lib.MPIR_Hip_cas_indexed_ordered.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, i32, vp, i32]
+    lib.MPIR_Hip_cas_indexed_ordered.restype = i32
+    lib.MPIR_Hip_cas_plan_info.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, i32, ctypes.POINTER(u64)]
+    lib.MPIR_Hip_cas_plan_info.restype = i32
     lib.MPIX_Hip_comm_get_unique_id.argtypes = [vp]
     lib.MPIX_Hip_comm_get_unique_id.restype = i32
     lib.MPIX_Hip_comm_create.argtypes = [vp, i32, i32, ctypes.POINTER(vp)]
@@ -796,6 +803,49 @@ def fetch_indexed_ordered_plan_info(inbuf: int, in_displs, inoutbuf: int, inout_
     if rc:
         raise LookupError(f"MPIR_Hip_fetch_indexed_ordered_plan_info: {rc}")
     return dict(zip(("form", "launches", "groups", "per", "threshold", "rows_per_launch"), (int(v) for v in out)))
+
+
+# ---- ordered compare-and-swap (MPIX_Compare_and_swap_indexed_ordered)
+CAS_EMPTY, CAS_CONTIG_TILE, CAS_CONTIG_ELEMS, CAS_INDEXED = range(4)
+CAS_NAMES = ["empty", "contig_tile", "contig_elems", "indexed"]
+
+
+def compare_and_swap_indexed_ordered(origin: int, compare: int, target: int, target_displs, result: int, order,
+                                     disp_unit: int, count: int, datatype: int, stream: int = 0) -> int:
+    """MPIX_Compare_and_swap_indexed_ordered: count compare-and-swaps of one element
+    each, in table order.  origin, compare and result are packed by entry number
+    (raw device addresses); entry k's target is target + target_displs[k] *
+    disp_unit bytes.  result[k] receives what the target held before entry k; where
+    that equals compare[k] the target receives origin[k].  order: as for
+    reduce_local_indexed_ordered, or None with target_displs given: equal entries
+    are adjacent.  target_displs None: a contiguous target.  Tables and stream as
+    for reduce_local_indexed_ordered."""
+    return load().MPIX_Compare_and_swap_indexed_ordered(
+        ctypes.c_void_p(origin or None), ctypes.c_void_p(compare or None), ctypes.c_void_p(target or None),
+        ctypes.c_void_p(_table_addr(target_displs) or None), ctypes.c_void_p(result or None),
+        ctypes.c_void_p(_order_addr(order) or None), disp_unit, count, datatype, ctypes.c_void_p(stream or None))
+
+
+def cas_plan_info(origin: int, compare: int, target: int, target_displs, result: int, order, disp_unit: int,
+                  count: int, datatype: int) -> dict:
+    """MPIR_Hip_cas_plan_info: the launches of an ordered compare-and-swap of device
+    operands at these addresses (never dereferenced, the tables only compared with
+    0; no GPU needed): form (CAS_*), launches, groups, rows_per_launch (sorted
+    positions of a full launch), per (entries one workgroup owns), ahead (kCasAhead,
+    the positions a run is walked at a time), nhead and ntail (the elements
+    workgroup 0 of the tile form takes).  Raises LookupError where the element's
+    size has no kernel, ValueError for arguments the call refuses."""
+    out = (ctypes.c_uint64 * 8)()
+    rc = load().MPIR_Hip_cas_plan_info(
+        ctypes.c_void_p(origin or None), ctypes.c_void_p(compare or None), ctypes.c_void_p(target or None),
+        ctypes.c_void_p(_table_addr(target_displs) or None), ctypes.c_void_p(result or None),
+        ctypes.c_void_p(_order_addr(order) or None), disp_unit, count, _ELEM_BY_HANDLE[datatype], out)
+    if rc == MPIR_HIP_EARG:
+        raise ValueError("MPIR_Hip_cas_plan_info: arguments refused")
+    if rc:
+        raise LookupError(f"MPIR_Hip_cas_plan_info: {rc}")
+    return dict(zip(("form", "launches", "groups", "rows_per_launch", "per", "ahead", "nhead", "ntail"),
+                    (int(v) for v in out)))
 
 
 MPIX_HIP_ALG_AUTO = 0
