@@ -1,8 +1,9 @@
 // shim_ctx.hpp -- what the units of the C-ABI shim share (hip_reduce.hip: the
-// tables, knobs, routes and entry points; classify.hip: the pointer
-// classifier): the per-thread context pool with its streams, events and
-// buffers, the error text, DeviceScope, the operand classes and the
-// classifier's and direct_dispatch.hip's interfaces.
+// tables, knobs, the single call's routes and the combine; table_calls.hip: the
+// calls on many blocks at once; classify.hip: the pointer classifier): the
+// per-thread context pool with its streams, events and buffers, the error text,
+// DeviceScope, the operand classes, the classifier's and direct_dispatch.hip's
+// interfaces and what hip_reduce.hip lends table_calls.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -33,6 +34,14 @@ void direct_placement(int dev, int out[5]);
 size_t order_worksize(uint64_t n);
 hipError_t order_sort(const int64_t *displs, uint64_t n, int *order, void *work, size_t work_bytes, hipStream_t s,
                       size_t *need);
+
+// hip_reduce.hip, for table_calls.hip (the library does not export them): an
+// element class's bytes, the range check of (op, elem), and a synchronous call's wait
+#pragma GCC visibility push(hidden)
+extern const size_t g_elem_size[MPIR_HIP_NELEMS];
+bool pair_in_range(int op, int elem);
+int wait_stream(int dev, hipStream_t s);
+#pragma GCC visibility pop
 
 // ------------------------------------------------------------ per-thread state
 constexpr int kMaxDev = 64;

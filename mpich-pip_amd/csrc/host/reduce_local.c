@@ -401,25 +401,76 @@ static int reduce_local_multi(const void *const *inbufs, int n, void *outbuf, in
     return MPI_SUCCESS;
 }
 
-/* ---- MPIX_Reduce_local_batch: many segments, one launch (see the header) */
-/* The shim's batch entry is bound weakly, so that a program which links this
- * file against a partial shim of its own (a harness that stubs only the
- * MPIR_Hip_* entries its collectives reach) still links; without the entry the
- * call fails with MPI_ERR_OTHER. */
-#pragma weak MPIR_Hip_reduce_batch
-static int reduce_local_batch(const MPIX_Reduce_local_seg * segs, int nsegs, MPI_Datatype datatype,
-                              MPI_Op op, void *hip_stream);
+/* ---- what the MPIX calls on many blocks share --------------------------- */
+/* Each of them is a static body under the GLOBAL critical section (they
+ * validate user-op handles like MPI_Reduce_local does): the public entry
+ * returns CS_RETURN(body(...)). */
+#define CS_RETURN(call) do { \
+        int cs_rc_; \
+        MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL); \
+        cs_rc_ = (call); \
+        MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL); \
+        return cs_rc_; \
+    } while (0)
 
-int MPIX_Reduce_local_batch(const MPIX_Reduce_local_seg * segs, int nsegs, MPI_Datatype datatype,
-                            MPI_Op op, void *hip_stream)
+/* A predefined op and its element class for the datatype in *opidx and *elem, or
+ * MPI_ERR_OP with the detail set: a user op, or the compute switch's `default:`
+ * (LAND / LOR on floats) */
+static int builtin_op_elem(MPI_Datatype datatype, MPI_Op op, int *opidx, int *elem)
 {
-    int rc;
-    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
-    rc = reduce_local_batch(segs, nsegs, datatype, op, hip_stream);
-    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
-    return rc;
+    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
+        MPIR_Err_set_detail("user MPI_Op functions run on the host; use MPI_Reduce_local");
+        return MPI_ERR_OP;
+    }
+    *opidx = op & 0xf;
+    *elem = MPIR_Op_resolve_elem(*opidx, datatype);
+    if (!*elem) {
+        MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
+        return MPI_ERR_OP;
+    }
+    return MPI_SUCCESS;
 }
 
+/* The shim's entries are bound weakly, so that a program which links this file
+ * against a partial shim of its own (a harness that stubs only the MPIR_Hip_*
+ * entries its collectives reach) still links; without the entry the call fails
+ * with MPI_ERR_OTHER. */
+static int shim_has(int bound, const char *entry)
+{
+    if (bound)
+        return MPI_SUCCESS;
+    MPIR_Err_set_detail("the HIP shim linked here has no %s", entry);
+    return MPI_ERR_OTHER;
+}
+
+/* The shim's return code as the MPI error of the call `fc`: MPIR_HIP_EBUFFER is
+ * MPI_ERR_BUFFER with the text `ebuffer`, MPIR_HIP_EARG (where the call has a
+ * text for it) MPI_ERR_ARG with `earg`, both formats of fc; anything else as
+ * MPIR_Op_report_hip_error reports it. */
+static int shim_result(const char *fc, int rc, const char *ebuffer, const char *earg)
+{
+    if (rc == MPIR_HIP_OK)
+        return MPI_SUCCESS;
+    if (rc == MPIR_HIP_EBUFFER) {
+        MPIR_Err_set_detail(ebuffer, fc);
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (rc == MPIR_HIP_EARG && earg) {
+        MPIR_Err_set_detail(earg, fc);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    MPIR_Op_report_hip_error(fc, rc);
+    return err_return(fc, *MPIR_Op_errno_ptr());
+}
+
+static const char EBUF_BUFFERS[] = "%s needs device-resident buffers on one device";
+static const char EBUF_TABLES[] = "%s needs device-resident operands on one device, and its tables there too "
+    "(host tables: the synchronous call only)";
+static const char EARG_RAGGED[] = "%s: starts is not 0, non-decreasing and ending at count, or a piece's offset does "
+    "not fit the address space";
+
+/* ---- MPIX_Reduce_local_batch: many segments, one launch (see the header) */
+#pragma weak MPIR_Hip_reduce_batch
 static int reduce_local_batch(const MPIX_Reduce_local_seg * segs, int nsegs, MPI_Datatype datatype,
                               MPI_Op op, void *hip_stream)
 {
@@ -445,20 +496,9 @@ static int reduce_local_batch(const MPIX_Reduce_local_seg * segs, int nsegs, MPI
     }
     if (!nonempty)
         return MPI_SUCCESS;
-    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
-        MPIR_Err_set_detail("user MPI_Op functions run on the host; use MPI_Reduce_local");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    opidx = op & 0xf;
-    elem = MPIR_Op_resolve_elem(opidx, datatype);
-    if (!elem) {        /* compute switch `default:` (LAND/LOR on floats) */
-        MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    if (!MPIR_Hip_reduce_batch) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_batch");
-        return err_return(fc, MPI_ERR_OTHER);
-    }
+    if ((mpi_errno = builtin_op_elem(datatype, op, &opidx, &elem)) != MPI_SUCCESS ||
+        (mpi_errno = shim_has(MPIR_Hip_reduce_batch != NULL, "MPIR_Hip_reduce_batch")) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
     if (nsegs > (int) (sizeof small / sizeof small[0])) {
         hs = (MPIR_Hip_seg *) malloc((size_t) nsegs * sizeof *hs);
         if (!hs) {
@@ -474,33 +514,17 @@ static int reduce_local_batch(const MPIX_Reduce_local_seg * segs, int nsegs, MPI
     rc = MPIR_Hip_reduce_batch(hs, nsegs, opidx, elem, hip_stream, hip_stream == NULL);
     if (hs != small)
         free(hs);
-    if (rc == MPIR_HIP_EBUFFER) {
-        MPIR_Err_set_detail("%s needs device-resident buffers on one device", fc);
-        return err_return(fc, MPI_ERR_BUFFER);
-    }
-    if (rc != MPIR_HIP_OK) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return err_return(fc, *MPIR_Op_errno_ptr());
-    }
-    return MPI_SUCCESS;
+    return shim_result(fc, rc, EBUF_BUFFERS, NULL);
+}
+
+int MPIX_Reduce_local_batch(const MPIX_Reduce_local_seg * segs, int nsegs, MPI_Datatype datatype,
+                            MPI_Op op, void *hip_stream)
+{
+    CS_RETURN(reduce_local_batch(segs, nsegs, datatype, op, hip_stream));
 }
 
 /* ---- MPIX_Reduce_local_strided: equal rows at one stride (see the header) */
-/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
 #pragma weak MPIR_Hip_reduce_strided
-static int reduce_local_strided(const void *inbuf, MPI_Aint in_stride, void *inoutbuf, MPI_Aint inout_stride,
-                                int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream);
-
-int MPIX_Reduce_local_strided(const void *inbuf, MPI_Aint in_stride, void *inoutbuf, MPI_Aint inout_stride,
-                              int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
-{
-    int rc;
-    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
-    rc = reduce_local_strided(inbuf, in_stride, inoutbuf, inout_stride, nblocks, blocklen, datatype, op, hip_stream);
-    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
-    return rc;
-}
-
 static int reduce_local_strided(const void *inbuf, MPI_Aint in_stride, void *inoutbuf, MPI_Aint inout_stride,
                                 int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
 {
@@ -522,58 +546,29 @@ static int reduce_local_strided(const void *inbuf, MPI_Aint in_stride, void *ino
     }
     if (empty)
         return MPI_SUCCESS;
-    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
-        MPIR_Err_set_detail("user MPI_Op functions run on the host; use MPI_Reduce_local");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    opidx = op & 0xf;
-    elem = MPIR_Op_resolve_elem(opidx, datatype);
-    if (!elem) {        /* compute switch `default:` (LAND/LOR on floats) */
-        MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
-        return err_return(fc, MPI_ERR_OP);
-    }
+    if ((mpi_errno = builtin_op_elem(datatype, op, &opidx, &elem)) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
     if (nblocks > 1 && (uint64_t) inout_stride < (uint64_t) blocklen * MPIR_Hip_elem_size(elem)) {
         MPIR_Err_set_detail("inout_stride %ld is below the row's %lu bytes: output rows would overlap",
                             (long) inout_stride, (unsigned long) blocklen * MPIR_Hip_elem_size(elem));
         return err_return(fc, MPI_ERR_ARG);
     }
-    if (!MPIR_Hip_reduce_strided) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_strided");
-        return err_return(fc, MPI_ERR_OTHER);
-    }
+    if ((mpi_errno = shim_has(MPIR_Hip_reduce_strided != NULL, "MPIR_Hip_reduce_strided")) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
     rc = MPIR_Hip_reduce_strided(inbuf, (uint64_t) in_stride, inoutbuf, (uint64_t) inout_stride, (uint64_t) nblocks,
                                  (uint64_t) blocklen, opidx, elem, hip_stream, hip_stream == NULL);
-    if (rc == MPIR_HIP_EBUFFER) {
-        MPIR_Err_set_detail("%s needs device-resident buffers on one device", fc);
-        return err_return(fc, MPI_ERR_BUFFER);
-    }
-    if (rc == MPIR_HIP_EARG) {
-        MPIR_Err_set_detail("%s: the rows' span does not fit the address space", fc);
-        return err_return(fc, MPI_ERR_ARG);
-    }
-    if (rc != MPIR_HIP_OK) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return err_return(fc, *MPIR_Op_errno_ptr());
-    }
-    return MPI_SUCCESS;
+    return shim_result(fc, rc, EBUF_BUFFERS, "%s: the rows' span does not fit the address space");
+}
+
+int MPIX_Reduce_local_strided(const void *inbuf, MPI_Aint in_stride, void *inoutbuf, MPI_Aint inout_stride,
+                              int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    CS_RETURN(reduce_local_strided(inbuf, in_stride, inoutbuf, inout_stride, nblocks, blocklen, datatype, op,
+                                   hip_stream));
 }
 
 /* ---- MPIX_Reduce_local_fetch: old value out, combine in (see the header) */
-/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
 #pragma weak MPIR_Hip_reduce_fetch
-static int reduce_local_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, int count, MPI_Datatype datatype,
-                              MPI_Op op, void *hip_stream);
-
-int MPIX_Reduce_local_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, int count, MPI_Datatype datatype,
-                            MPI_Op op, void *hip_stream)
-{
-    int rc;
-    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
-    rc = reduce_local_fetch(inbuf, inoutbuf, fetchbuf, count, datatype, op, hip_stream);
-    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
-    return rc;
-}
-
 static int ranges_overlap(const void *a, const void *b, uint64_t bytes)
 {
     const uintptr_t pa = (uintptr_t) a, pb = (uintptr_t) b;
@@ -658,41 +653,20 @@ static int reduce_local_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf,
         MPIR_Err_set_detail("fetchbuf overlaps %s", ranges_overlap(fetchbuf, inoutbuf, bytes) ? "inoutbuf" : "inbuf");
         return err_return(fc, MPI_ERR_BUFFER);
     }
-    if (!MPIR_Hip_reduce_fetch) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_fetch");
-        return err_return(fc, MPI_ERR_OTHER);
-    }
+    if ((mpi_errno = shim_has(MPIR_Hip_reduce_fetch != NULL, "MPIR_Hip_reduce_fetch")) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
     rc = MPIR_Hip_reduce_fetch(inbuf, inoutbuf, fetchbuf, n, opidx, elem, hip_stream, hip_stream == NULL);
-    if (rc == MPIR_HIP_EBUFFER) {
-        MPIR_Err_set_detail("%s needs device-resident buffers on one device", fc);
-        return err_return(fc, MPI_ERR_BUFFER);
-    }
-    if (rc != MPIR_HIP_OK) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return err_return(fc, *MPIR_Op_errno_ptr());
-    }
-    return MPI_SUCCESS;
+    return shim_result(fc, rc, EBUF_BUFFERS, NULL);
+}
+
+int MPIX_Reduce_local_fetch(const void *inbuf, void *inoutbuf, void *fetchbuf, int count, MPI_Datatype datatype,
+                            MPI_Op op, void *hip_stream)
+{
+    CS_RETURN(reduce_local_fetch(inbuf, inoutbuf, fetchbuf, count, datatype, op, hip_stream));
 }
 
 /* ---- MPIX_Reduce_local_indexed: equal blocks at a displacement table (see the header) */
-/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
 #pragma weak MPIR_Hip_reduce_indexed
-static int reduce_local_indexed(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
-                                const MPI_Aint * inout_displs, MPI_Aint disp_unit, int nblocks, int blocklen,
-                                MPI_Datatype datatype, MPI_Op op, void *hip_stream);
-
-int MPIX_Reduce_local_indexed(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
-                              const MPI_Aint * inout_displs, MPI_Aint disp_unit, int nblocks, int blocklen,
-                              MPI_Datatype datatype, MPI_Op op, void *hip_stream)
-{
-    int rc;
-    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
-    rc = reduce_local_indexed(inbuf, in_displs, inoutbuf, inout_displs, disp_unit, nblocks, blocklen, datatype, op,
-                              hip_stream);
-    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
-    return rc;
-}
-
 static int reduce_local_indexed(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
                                 const MPI_Aint * inout_displs, MPI_Aint disp_unit, int nblocks, int blocklen,
                                 MPI_Datatype datatype, MPI_Op op, void *hip_stream)
@@ -716,67 +690,27 @@ static int reduce_local_indexed(const void *inbuf, const MPI_Aint * in_displs, v
     }
     if (empty)
         return MPI_SUCCESS;
-    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
-        MPIR_Err_set_detail("user MPI_Op functions run on the host; use MPI_Reduce_local");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    opidx = op & 0xf;
-    elem = MPIR_Op_resolve_elem(opidx, datatype);
-    if (!elem) {        /* compute switch `default:` (LAND/LOR on floats) */
-        MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    if (!MPIR_Hip_reduce_indexed) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_indexed");
-        return err_return(fc, MPI_ERR_OTHER);
-    }
+    if ((mpi_errno = builtin_op_elem(datatype, op, &opidx, &elem)) != MPI_SUCCESS ||
+        (mpi_errno = shim_has(MPIR_Hip_reduce_indexed != NULL, "MPIR_Hip_reduce_indexed")) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
     rc = MPIR_Hip_reduce_indexed(inbuf, (const int64_t *) in_displs, inoutbuf, (const int64_t *) inout_displs,
                                  (uint64_t) disp_unit, (uint64_t) nblocks, (uint64_t) blocklen, opidx, elem,
                                  hip_stream, hip_stream == NULL);
-    if (rc == MPIR_HIP_EBUFFER) {
-        MPIR_Err_set_detail("%s needs device-resident operands on one device, and its tables there too "
-                            "(host tables: the synchronous call only)", fc);
-        return err_return(fc, MPI_ERR_BUFFER);
-    }
-    if (rc == MPIR_HIP_EARG) {
-        MPIR_Err_set_detail("%s: a block's offset does not fit the address space", fc);
-        return err_return(fc, MPI_ERR_ARG);
-    }
-    if (rc != MPIR_HIP_OK) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return err_return(fc, *MPIR_Op_errno_ptr());
-    }
-    return MPI_SUCCESS;
+    return shim_result(fc, rc, EBUF_TABLES, "%s: a block's offset does not fit the address space");
+}
+
+int MPIX_Reduce_local_indexed(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                              const MPI_Aint * inout_displs, MPI_Aint disp_unit, int nblocks, int blocklen,
+                              MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    CS_RETURN(reduce_local_indexed(inbuf, in_displs, inoutbuf, inout_displs, disp_unit, nblocks, blocklen, datatype,
+                                   op, hip_stream));
 }
 
 /* ---- MPIX_Reduce_local_indexed_ordered: repeated targets in table order (see the header) */
-/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
 #pragma weak MPIR_Hip_reduce_indexed_ordered
 #pragma weak MPIR_Hip_order_build
 #pragma weak MPIR_Hip_order_worksize
-static int reduce_local_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
-                                        const MPI_Aint * inout_displs, const int *order, MPI_Aint disp_unit,
-                                        int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op,
-                                        void *hip_stream);
-static int reduce_local_order(const MPI_Aint * displs, int nblocks, int *order, void *work, MPI_Aint work_bytes,
-                              void *hip_stream);
-
-int MPIX_Reduce_local_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
-                                      const MPI_Aint * inout_displs, const int *order, MPI_Aint disp_unit,
-                                      int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
-{
-    int rc;
-    /* no order table: the indexed call unchanged, its own name on the error stack */
-    if (order == NULL)
-        return MPIX_Reduce_local_indexed(inbuf, in_displs, inoutbuf, inout_displs, disp_unit, nblocks, blocklen,
-                                         datatype, op, hip_stream);
-    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
-    rc = reduce_local_indexed_ordered(inbuf, in_displs, inoutbuf, inout_displs, order, disp_unit, nblocks, blocklen,
-                                      datatype, op, hip_stream);
-    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
-    return rc;
-}
-
 static int reduce_local_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
                                         const MPI_Aint * inout_displs, const int *order, MPI_Aint disp_unit,
                                         int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op,
@@ -804,38 +738,26 @@ static int reduce_local_indexed_ordered(const void *inbuf, const MPI_Aint * in_d
         MPIR_Err_set_detail("an order table with no inout_displs: a packed target has no repeats to order");
         return err_return(fc, MPI_ERR_ARG);
     }
-    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
-        MPIR_Err_set_detail("user MPI_Op functions run on the host; use MPI_Reduce_local");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    opidx = op & 0xf;
-    elem = MPIR_Op_resolve_elem(opidx, datatype);
-    if (!elem) {        /* compute switch `default:` (LAND/LOR on floats) */
-        MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    if (!MPIR_Hip_reduce_indexed_ordered) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_indexed_ordered");
-        return err_return(fc, MPI_ERR_OTHER);
-    }
+    if ((mpi_errno = builtin_op_elem(datatype, op, &opidx, &elem)) != MPI_SUCCESS ||
+        (mpi_errno = shim_has(MPIR_Hip_reduce_indexed_ordered != NULL, "MPIR_Hip_reduce_indexed_ordered")) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
     rc = MPIR_Hip_reduce_indexed_ordered(inbuf, (const int64_t *) in_displs, inoutbuf, (const int64_t *) inout_displs,
                                          order, (uint64_t) disp_unit, (uint64_t) nblocks, (uint64_t) blocklen, opidx,
                                          elem, hip_stream, hip_stream == NULL);
-    if (rc == MPIR_HIP_EBUFFER) {
-        MPIR_Err_set_detail("%s needs device-resident operands on one device, and its tables there too "
-                            "(host tables: the synchronous call only)", fc);
-        return err_return(fc, MPI_ERR_BUFFER);
-    }
-    if (rc == MPIR_HIP_EARG) {
-        MPIR_Err_set_detail("%s: a block's offset does not fit the address space, or the order table is not "
-                            "a stable sort of inout_displs", fc);
-        return err_return(fc, MPI_ERR_ARG);
-    }
-    if (rc != MPIR_HIP_OK) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return err_return(fc, *MPIR_Op_errno_ptr());
-    }
-    return MPI_SUCCESS;
+    return shim_result(fc, rc, EBUF_TABLES, "%s: a block's offset does not fit the address space, or the order table "
+                       "is not a stable sort of inout_displs");
+}
+
+int MPIX_Reduce_local_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                                      const MPI_Aint * inout_displs, const int *order, MPI_Aint disp_unit,
+                                      int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    /* no order table: the indexed call unchanged, its own name on the error stack */
+    if (order == NULL)
+        return MPIX_Reduce_local_indexed(inbuf, in_displs, inoutbuf, inout_displs, disp_unit, nblocks, blocklen,
+                                         datatype, op, hip_stream);
+    CS_RETURN(reduce_local_indexed_ordered(inbuf, in_displs, inoutbuf, inout_displs, order, disp_unit, nblocks,
+                                           blocklen, datatype, op, hip_stream));
 }
 
 int MPIX_Reduce_local_order_worksize(int nblocks, MPI_Aint * work_bytes)
@@ -850,23 +772,12 @@ int MPIX_Reduce_local_order_worksize(int nblocks, MPI_Aint * work_bytes)
     } else if (work_bytes == NULL) {
         MPIR_Err_set_detail("work_bytes is NULL");
         rc = err_return(fc, MPI_ERR_ARG);
-    } else if (!MPIR_Hip_order_worksize) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_order_worksize");
-        rc = err_return(fc, MPI_ERR_OTHER);
+    } else if ((rc = shim_has(MPIR_Hip_order_worksize != NULL, "MPIR_Hip_order_worksize")) != MPI_SUCCESS) {
+        rc = err_return(fc, rc);
     } else {
         (void) MPIR_Hip_order_worksize((uint64_t) nblocks, &bytes);     /* (an int is always in its range) */
         *work_bytes = (MPI_Aint) bytes;
     }
-    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
-    return rc;
-}
-
-int MPIX_Reduce_local_order(const MPI_Aint * displs, int nblocks, int *order, void *work, MPI_Aint work_bytes,
-                            void *hip_stream)
-{
-    int rc;
-    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
-    rc = reduce_local_order(displs, nblocks, order, work, work_bytes, hip_stream);
     MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
     return rc;
 }
@@ -890,48 +801,27 @@ static int reduce_local_order(const MPI_Aint * displs, int nblocks, int *order, 
         MPIR_Err_set_detail("negative work_bytes %ld", (long) work_bytes);
         return err_return(fc, MPI_ERR_ARG);
     }
-    if (!MPIR_Hip_order_build) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_order_build");
-        return err_return(fc, MPI_ERR_OTHER);
-    }
+    if ((rc = shim_has(MPIR_Hip_order_build != NULL, "MPIR_Hip_order_build")) != MPI_SUCCESS)
+        return err_return(fc, rc);
     rc = MPIR_Hip_order_build((const int64_t *) displs, (uint64_t) nblocks, order, work, (uint64_t) work_bytes,
                               hip_stream, hip_stream == NULL);
-    if (rc == MPIR_HIP_EBUFFER) {
-        MPIR_Err_set_detail("%s needs its tables and work in device memory on one device (host tables, or no "
-                            "work: the synchronous call only)", fc);
-        return err_return(fc, MPI_ERR_BUFFER);
-    }
-    if (rc == MPIR_HIP_EARG) {
+    if (rc == MPIR_HIP_EARG) {  /* (its text has an argument of its own) */
         MPIR_Err_set_detail("%s: work_bytes %ld is less than MPIX_Reduce_local_order_worksize reports", fc,
                             (long) work_bytes);
         return err_return(fc, MPI_ERR_ARG);
     }
-    if (rc != MPIR_HIP_OK) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return err_return(fc, *MPIR_Op_errno_ptr());
-    }
-    return MPI_SUCCESS;
+    return shim_result(fc, rc, "%s needs its tables and work in device memory on one device (host tables, or no "
+                       "work: the synchronous call only)", NULL);
+}
+
+int MPIX_Reduce_local_order(const MPI_Aint * displs, int nblocks, int *order, void *work, MPI_Aint work_bytes,
+                            void *hip_stream)
+{
+    CS_RETURN(reduce_local_order(displs, nblocks, order, work, work_bytes, hip_stream));
 }
 
 /* ---- MPIX_Reduce_local_ragged: unequal pieces from a table of packed offsets (see the header) */
-/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
 #pragma weak MPIR_Hip_reduce_ragged
-static int reduce_local_ragged(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
-                               const MPI_Aint * inout_displs, const MPI_Aint * starts, MPI_Aint disp_unit,
-                               int npieces, int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream);
-
-int MPIX_Reduce_local_ragged(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
-                             const MPI_Aint * inout_displs, const MPI_Aint * starts, MPI_Aint disp_unit,
-                             int npieces, int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
-{
-    int rc;
-    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
-    rc = reduce_local_ragged(inbuf, in_displs, inoutbuf, inout_displs, starts, disp_unit, npieces, count, datatype,
-                             op, hip_stream);
-    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
-    return rc;
-}
-
 static int reduce_local_ragged(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
                                const MPI_Aint * inout_displs, const MPI_Aint * starts, MPI_Aint disp_unit,
                                int npieces, int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
@@ -963,58 +853,25 @@ static int reduce_local_ragged(const void *inbuf, const MPI_Aint * in_displs, vo
         MPIR_Err_set_detail("a displacement table needs starts");
         return err_return(fc, MPI_ERR_ARG);
     }
-    if (HANDLE_GET_KIND(op) != HANDLE_KIND_BUILTIN) {
-        MPIR_Err_set_detail("user MPI_Op functions run on the host; use MPI_Reduce_local");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    opidx = op & 0xf;
-    elem = MPIR_Op_resolve_elem(opidx, datatype);
-    if (!elem) {        /* compute switch `default:` (LAND/LOR on floats) */
-        MPIR_Err_set_detail("MPI_Op operation not defined for this datatype");
-        return err_return(fc, MPI_ERR_OP);
-    }
-    if (!MPIR_Hip_reduce_ragged) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_ragged");
-        return err_return(fc, MPI_ERR_OTHER);
-    }
+    if ((mpi_errno = builtin_op_elem(datatype, op, &opidx, &elem)) != MPI_SUCCESS ||
+        (mpi_errno = shim_has(MPIR_Hip_reduce_ragged != NULL, "MPIR_Hip_reduce_ragged")) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
     rc = MPIR_Hip_reduce_ragged(inbuf, (const int64_t *) in_displs, inoutbuf, (const int64_t *) inout_displs,
                                 (const int64_t *) starts, (uint64_t) disp_unit, (uint64_t) npieces, (uint64_t) count,
                                 opidx, elem, hip_stream, hip_stream == NULL);
-    if (rc == MPIR_HIP_EBUFFER) {
-        MPIR_Err_set_detail("%s needs device-resident operands on one device, and its tables there too "
-                            "(host tables: the synchronous call only)", fc);
-        return err_return(fc, MPI_ERR_BUFFER);
-    }
-    if (rc == MPIR_HIP_EARG) {
-        MPIR_Err_set_detail("%s: starts is not 0, non-decreasing and ending at count, or a piece's offset does not "
-                            "fit the address space", fc);
-        return err_return(fc, MPI_ERR_ARG);
-    }
-    if (rc != MPIR_HIP_OK) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return err_return(fc, *MPIR_Op_errno_ptr());
-    }
-    return MPI_SUCCESS;
+    return shim_result(fc, rc, EBUF_TABLES, EARG_RAGGED);
+}
+
+int MPIX_Reduce_local_ragged(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                             const MPI_Aint * inout_displs, const MPI_Aint * starts, MPI_Aint disp_unit,
+                             int npieces, int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    CS_RETURN(reduce_local_ragged(inbuf, in_displs, inoutbuf, inout_displs, starts, disp_unit, npieces, count,
+                                  datatype, op, hip_stream));
 }
 
 /* ---- MPIX_Reduce_local_fetch_ragged: the fetching reduction on a ragged target (see the header) */
-/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
 #pragma weak MPIR_Hip_reduce_fetch_ragged
-static int reduce_local_fetch_ragged(const void *inbuf, void *inoutbuf, const MPI_Aint * inout_displs,
-                                     void *fetchbuf, const MPI_Aint * starts, MPI_Aint disp_unit, int npieces,
-                                     int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream);
-
-int MPIX_Reduce_local_fetch_ragged(const void *inbuf, void *inoutbuf, const MPI_Aint * inout_displs,
-                                   void *fetchbuf, const MPI_Aint * starts, MPI_Aint disp_unit, int npieces,
-                                   int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
-{
-    int rc;
-    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
-    rc = reduce_local_fetch_ragged(inbuf, inoutbuf, inout_displs, fetchbuf, starts, disp_unit, npieces, count,
-                                   datatype, op, hip_stream);
-    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
-    return rc;
-}
 
 /* The op rule of the fetching calls whose byte ops are kernels (the ragged and
  * the ordered indexed one): *opidx and *elem of (datatype, op), or the error
@@ -1134,51 +991,25 @@ static int reduce_local_fetch_ragged(const void *inbuf, void *inoutbuf, const MP
         MPIR_Err_set_detail("fetchbuf overlaps %s", !no_op && ranges_overlap(fetchbuf, inbuf, bytes) ? "inbuf" : "inoutbuf");
         return err_return(fc, MPI_ERR_BUFFER);
     }
-    if (!MPIR_Hip_reduce_fetch_ragged) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_fetch_ragged");
-        return err_return(fc, MPI_ERR_OTHER);
-    }
+    if ((mpi_errno = shim_has(MPIR_Hip_reduce_fetch_ragged != NULL, "MPIR_Hip_reduce_fetch_ragged")) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
     rc = MPIR_Hip_reduce_fetch_ragged(inbuf, inoutbuf, (const int64_t *) inout_displs, fetchbuf,
                                       (const int64_t *) starts, (uint64_t) disp_unit, (uint64_t) npieces,
                                       (uint64_t) count, opidx, elem, hip_stream, hip_stream == NULL);
-    if (rc == MPIR_HIP_EBUFFER) {
-        MPIR_Err_set_detail("%s needs device-resident buffers on one device, its tables there too (host tables: the "
-                            "synchronous call only), and fetchbuf outside the pieces' extent", fc);
-        return err_return(fc, MPI_ERR_BUFFER);
-    }
-    if (rc == MPIR_HIP_EARG) {
-        MPIR_Err_set_detail("%s: starts is not 0, non-decreasing and ending at count, or a piece's offset does not "
-                            "fit the address space", fc);
-        return err_return(fc, MPI_ERR_ARG);
-    }
-    if (rc != MPIR_HIP_OK) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return err_return(fc, *MPIR_Op_errno_ptr());
-    }
-    return MPI_SUCCESS;
+    return shim_result(fc, rc, "%s needs device-resident buffers on one device, its tables there too (host tables: "
+                       "the synchronous call only), and fetchbuf outside the pieces' extent", EARG_RAGGED);
+}
+
+int MPIX_Reduce_local_fetch_ragged(const void *inbuf, void *inoutbuf, const MPI_Aint * inout_displs,
+                                   void *fetchbuf, const MPI_Aint * starts, MPI_Aint disp_unit, int npieces,
+                                   int count, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    CS_RETURN(reduce_local_fetch_ragged(inbuf, inoutbuf, inout_displs, fetchbuf, starts, disp_unit, npieces, count,
+                                        datatype, op, hip_stream));
 }
 
 /* ---- MPIX_Reduce_local_fetch_indexed_ordered: the ordered fetch-and-op (see the header) */
-/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
 #pragma weak MPIR_Hip_reduce_fetch_indexed_ordered
-static int reduce_local_fetch_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
-                                              const MPI_Aint * inout_displs, void *fetchbuf, const int *order,
-                                              MPI_Aint disp_unit, int nblocks, int blocklen, MPI_Datatype datatype,
-                                              MPI_Op op, void *hip_stream);
-
-int MPIX_Reduce_local_fetch_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
-                                            const MPI_Aint * inout_displs, void *fetchbuf, const int *order,
-                                            MPI_Aint disp_unit, int nblocks, int blocklen, MPI_Datatype datatype,
-                                            MPI_Op op, void *hip_stream)
-{
-    int rc;
-    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
-    rc = reduce_local_fetch_indexed_ordered(inbuf, in_displs, inoutbuf, inout_displs, fetchbuf, order, disp_unit,
-                                            nblocks, blocklen, datatype, op, hip_stream);
-    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
-    return rc;
-}
-
 static int reduce_local_fetch_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
                                               const MPI_Aint * inout_displs, void *fetchbuf, const int *order,
                                               MPI_Aint disp_unit, int nblocks, int blocklen, MPI_Datatype datatype,
@@ -1238,52 +1069,31 @@ static int reduce_local_fetch_indexed_ordered(const void *inbuf, const MPI_Aint 
                             !no_op && !in_displs && ranges_overlap(fetchbuf, inbuf, bytes) ? "inbuf" : "inoutbuf");
         return err_return(fc, MPI_ERR_BUFFER);
     }
-    if (!MPIR_Hip_reduce_fetch_indexed_ordered) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_reduce_fetch_indexed_ordered");
-        return err_return(fc, MPI_ERR_OTHER);
-    }
+    if ((mpi_errno = shim_has(MPIR_Hip_reduce_fetch_indexed_ordered != NULL,
+                              "MPIR_Hip_reduce_fetch_indexed_ordered")) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
     rc = MPIR_Hip_reduce_fetch_indexed_ordered(inbuf, no_op ? NULL : (const int64_t *) in_displs, inoutbuf,
                                                (const int64_t *) inout_displs, fetchbuf, order, (uint64_t) disp_unit,
                                                (uint64_t) nblocks, (uint64_t) blocklen, opidx, elem, hip_stream,
                                                hip_stream == NULL);
-    if (rc == MPIR_HIP_EBUFFER) {
-        MPIR_Err_set_detail("%s needs device-resident buffers on one device, its tables there too (host tables: the "
-                            "synchronous call only), and fetchbuf outside the target blocks' extent", fc);
-        return err_return(fc, MPI_ERR_BUFFER);
-    }
-    if (rc == MPIR_HIP_EARG) {
-        MPIR_Err_set_detail("%s: a block's offset does not fit the address space, the order table is not a stable "
-                            "sort of inout_displs, or with no order table equal entries of inout_displs are not "
-                            "adjacent", fc);
-        return err_return(fc, MPI_ERR_ARG);
-    }
-    if (rc != MPIR_HIP_OK) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return err_return(fc, *MPIR_Op_errno_ptr());
-    }
-    return MPI_SUCCESS;
+    return shim_result(fc, rc, "%s needs device-resident buffers on one device, its tables there too (host tables: "
+                       "the synchronous call only), and fetchbuf outside the target blocks' extent",
+                       "%s: a block's offset does not fit the address space, the order table is not a stable sort of "
+                       "inout_displs, or with no order table equal entries of inout_displs are not adjacent");
+}
+
+int MPIX_Reduce_local_fetch_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                                            const MPI_Aint * inout_displs, void *fetchbuf, const int *order,
+                                            MPI_Aint disp_unit, int nblocks, int blocklen, MPI_Datatype datatype,
+                                            MPI_Op op, void *hip_stream)
+{
+    CS_RETURN(reduce_local_fetch_indexed_ordered(inbuf, in_displs, inoutbuf, inout_displs, fetchbuf, order, disp_unit,
+                                                 nblocks, blocklen, datatype, op, hip_stream));
 }
 
 /* ---- MPIX_Compare_and_swap_indexed_ordered: batched CAS in table order (see the header) */
-/* (bound weakly for the reason MPIR_Hip_reduce_batch is) */
 #pragma weak MPIR_Hip_cas_indexed_ordered
 #pragma weak MPIR_Hip_cas_plan_info
-static int compare_and_swap_indexed_ordered(const void *origin, const void *compare, void *target,
-                                            const MPI_Aint * target_displs, void *result, const int *order,
-                                            MPI_Aint disp_unit, int count, MPI_Datatype datatype, void *hip_stream);
-
-int MPIX_Compare_and_swap_indexed_ordered(const void *origin, const void *compare, void *target,
-                                          const MPI_Aint * target_displs, void *result, const int *order,
-                                          MPI_Aint disp_unit, int count, MPI_Datatype datatype, void *hip_stream)
-{
-    int rc;
-    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
-    rc = compare_and_swap_indexed_ordered(origin, compare, target, target_displs, result, order, disp_unit, count,
-                                          datatype, hip_stream);
-    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
-    return rc;
-}
-
 /* MPIR_Type_is_rma_atomic (src/mpi/rma/rmatypeutil.c:23-43) for a build with no
  * Fortran and no C++: the C integer group and MPI_CHAR, MPI_AINT / MPI_OFFSET /
  * MPI_COUNT, MPI_C_BOOL and MPI_BYTE */
@@ -1352,28 +1162,22 @@ static int compare_and_swap_indexed_ordered(const void *origin, const void *comp
                             ranges_overlap(result, compare, bytes) ? "compare" : "target");
         return err_return(fc, MPI_ERR_BUFFER);
     }
-    if (!MPIR_Hip_cas_indexed_ordered) {
-        MPIR_Err_set_detail("the HIP shim linked here has no MPIR_Hip_cas_indexed_ordered");
-        return err_return(fc, MPI_ERR_OTHER);
-    }
+    if ((rc = shim_has(MPIR_Hip_cas_indexed_ordered != NULL, "MPIR_Hip_cas_indexed_ordered")) != MPI_SUCCESS)
+        return err_return(fc, rc);
     rc = MPIR_Hip_cas_indexed_ordered(origin, compare, target, (const int64_t *) target_displs, result, order,
                                       (uint64_t) disp_unit, (uint64_t) count, d->elem, hip_stream, hip_stream == NULL);
-    if (rc == MPIR_HIP_EBUFFER) {
-        MPIR_Err_set_detail("%s needs device-resident buffers on one device, its tables there too (host tables: the "
-                            "synchronous call only), and result outside the targets' extent", fc);
-        return err_return(fc, MPI_ERR_BUFFER);
-    }
-    if (rc == MPIR_HIP_EARG) {
-        MPIR_Err_set_detail("%s: a target's offset does not fit the address space, the order table is not a stable "
-                            "sort of target_displs, or with no order table equal entries of target_displs are not "
-                            "adjacent", fc);
-        return err_return(fc, MPI_ERR_ARG);
-    }
-    if (rc != MPIR_HIP_OK) {
-        MPIR_Op_report_hip_error(fc, rc);
-        return err_return(fc, *MPIR_Op_errno_ptr());
-    }
-    return MPI_SUCCESS;
+    return shim_result(fc, rc, "%s needs device-resident buffers on one device, its tables there too (host tables: "
+                       "the synchronous call only), and result outside the targets' extent",
+                       "%s: a target's offset does not fit the address space, the order table is not a stable sort of "
+                       "target_displs, or with no order table equal entries of target_displs are not adjacent");
+}
+
+int MPIX_Compare_and_swap_indexed_ordered(const void *origin, const void *compare, void *target,
+                                          const MPI_Aint * target_displs, void *result, const int *order,
+                                          MPI_Aint disp_unit, int count, MPI_Datatype datatype, void *hip_stream)
+{
+    CS_RETURN(compare_and_swap_indexed_ordered(origin, compare, target, target_displs, result, order, disp_unit,
+                                               count, datatype, hip_stream));
 }
 
 /* ---- MPI_Op_create / MPI_Op_free / MPI_Op_commutative ------------------ */
