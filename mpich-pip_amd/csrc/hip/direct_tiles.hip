@@ -192,24 +192,12 @@ __device__ __forceinline__ bool in_grid(const ElemsArgs &a) {
         if (GET(ks, &a) && in_grid(a)) reduce_elems<OP, T, false>(a.in, a.io, a.n, a.stride);             \
     }
 
-#define MPIR_DIRECT_TILE(OPN, OP, E, T) MPIR_DIRECT_KIND(, plain_args, OPN, OP, E, T) \
+#define MPIR_DIRECT_TILE(OP, OPN, E, T) MPIR_DIRECT_KIND(, plain_args, OPN, OP, E, T) \
                                         MPIR_DIRECT_KIND(c, checked_args, OPN, OP, E, T)
+#define MPIR_DIRECT_NONE(OP, OPN, E, T, EPL)
 
-// the (op, class) matrix of reg_sum_prod / reg_max_min / reg_logic / reg_pairs_x87
-#define X(E, T) MPIR_DIRECT_TILE(SUM, OpSum, E, T) MPIR_DIRECT_TILE(PROD, OpProd, E, T)
-FOR_INTS(X) FOR_REALS(X) FOR_CPLX(X) X(MPIR_HIP_F80, x80)
-#undef X
-#define X(E, T) MPIR_DIRECT_TILE(MAX, OpMax, E, T) MPIR_DIRECT_TILE(MIN, OpMin, E, T)
-FOR_INTS(X) FOR_REALS(X) X(MPIR_HIP_F80, x80)
-#undef X
-#define X(E, T) MPIR_DIRECT_TILE(LAND, OpLand, E, T) MPIR_DIRECT_TILE(LOR, OpLor, E, T) \
-                MPIR_DIRECT_TILE(BAND, OpBand, E, T) MPIR_DIRECT_TILE(BOR, OpBor, E, T) \
-                MPIR_DIRECT_TILE(BXOR, OpBxor, E, T)
-FOR_INTS(X)
-#undef X
-#define X(E, T) MPIR_DIRECT_TILE(LXOR, OpLxor, E, T)
-FOR_INTS(X) FOR_REALS(X) X(MPIR_HIP_F80, x80)
-#undef X
-#define X(E, T) MPIR_DIRECT_TILE(MAXLOC, OpMaxloc, E, T) MPIR_DIRECT_TILE(MINLOC, OpMinloc, E, T)
-FOR_PAIRS(X)
-#undef X
+// every pair on the ordinary launcher (kernel_table.hpp's lists); the wide pairs take the HIP launch
+MPIR_PAIRS_SUM_PROD(MPIR_DIRECT_TILE, MPIR_DIRECT_NONE)
+MPIR_PAIRS_MAX_MIN(MPIR_DIRECT_TILE, MPIR_DIRECT_NONE)
+MPIR_PAIRS_LOGIC(MPIR_DIRECT_TILE, MPIR_DIRECT_NONE)
+MPIR_PAIRS_PAIRS_X87(MPIR_DIRECT_TILE, MPIR_DIRECT_NONE)

@@ -14,8 +14,14 @@
 //                        P from 2 to 8 (a pairwise chain over p ranks is one pass
 //                        for any p <= 8).
 // Storage lives in hip_reduce.hip (zero-initialised); the reg_*.hip units fill
-// it from static constructors, one unit per op family so they compile in
-// parallel.  The ops a type admits follow src/include/mpir_op_util.h:263-364.
+// it from static constructors.  Which ops a class admits (src/include/
+// mpir_op_util.h:263-364) is stated once, in the four MPIR_PAIRS_* lists at the
+// end of this file, one per op group.  A unit is one macro call, MPIR_REG_UNIT or
+// MPIR_REG_FAMILY_UNIT: one kernel family's reg_*<> template over one list, so a
+// family is four units that compile in parallel, each its own code object.
+// direct_tiles.hip expands the same lists into its kernels.  The fused folds
+// (reg_multi*.hip), the byte ops of the fetching families and the CAS kernels
+// are partitioned by size, not by op group, and keep lists of their own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -281,12 +287,69 @@ void reg_multi(int op, int elem) {
 
 }  // namespace mpir_hip
 
-// Integer element classes and their device types.
-#define FOR_INTS(X) \
-    X(MPIR_HIP_I8, int8_t) X(MPIR_HIP_U8, uint8_t) X(MPIR_HIP_I16, int16_t) X(MPIR_HIP_U16, uint16_t) \
-    X(MPIR_HIP_I32, int32_t) X(MPIR_HIP_U32, uint32_t) X(MPIR_HIP_I64, int64_t) X(MPIR_HIP_U64, uint64_t)
-#define FOR_REALS(X) X(MPIR_HIP_F16, f16) X(MPIR_HIP_F32, float) X(MPIR_HIP_F64, double)
-#define FOR_CPLX(X) X(MPIR_HIP_CF32, cf32) X(MPIR_HIP_CF64, cf64)
-#define FOR_PAIRS(X) \
-    X(MPIR_HIP_P2INT, p2int) X(MPIR_HIP_PFLOATINT, pfloatint) X(MPIR_HIP_PLONGINT, plongint) \
-    X(MPIR_HIP_PSHORTINT, pshortint) X(MPIR_HIP_PDOUBLEINT, pdoubleint)
+// Element classes and their device types: X(E, T) for each class of the group;
+// whatever follows X in the call is handed on to it as further arguments.
+#define FOR_INTS(X, ...) \
+    X(MPIR_HIP_I8, int8_t, ##__VA_ARGS__) X(MPIR_HIP_U8, uint8_t, ##__VA_ARGS__) \
+    X(MPIR_HIP_I16, int16_t, ##__VA_ARGS__) X(MPIR_HIP_U16, uint16_t, ##__VA_ARGS__) \
+    X(MPIR_HIP_I32, int32_t, ##__VA_ARGS__) X(MPIR_HIP_U32, uint32_t, ##__VA_ARGS__) \
+    X(MPIR_HIP_I64, int64_t, ##__VA_ARGS__) X(MPIR_HIP_U64, uint64_t, ##__VA_ARGS__)
+#define FOR_REALS(X, ...) \
+    X(MPIR_HIP_F16, f16, ##__VA_ARGS__) X(MPIR_HIP_F32, float, ##__VA_ARGS__) X(MPIR_HIP_F64, double, ##__VA_ARGS__)
+#define FOR_CPLX(X, ...) X(MPIR_HIP_CF32, cf32, ##__VA_ARGS__) X(MPIR_HIP_CF64, cf64, ##__VA_ARGS__)
+#define FOR_PAIRS(X, ...) \
+    X(MPIR_HIP_P2INT, p2int, ##__VA_ARGS__) X(MPIR_HIP_PFLOATINT, pfloatint, ##__VA_ARGS__) \
+    X(MPIR_HIP_PLONGINT, plongint, ##__VA_ARGS__) X(MPIR_HIP_PSHORTINT, pshortint, ##__VA_ARGS__) \
+    X(MPIR_HIP_PDOUBLEINT, pdoubleint, ##__VA_ARGS__)
+
+// The (op, class) pairs that have kernels, stated once: four lists, one per op
+// group, which is also one registration unit per kernel family (they compile in
+// parallel).  Each list calls, in the order the kernels are instantiated,
+//   R(Op, OPN, E, T)       for a pair on the ordinary launcher,
+//   W(Op, OPN, E, T, EPL)  for a pair of the 32-byte classes on the wide one;
+// Op is the functor, OPN its bare name (MPIR_HIP_OP_##OPN is the op's index,
+// and direct_tiles.hip pastes OPN into its kernels' names), E the class, T its
+// device type.  118 pairs, 114 of them on R.  MPI_REPLACE, a byte copy of every
+// class and of the single call alone, is in no list (reg_pairs_x87.hip).
+#define MPIR_OPS_SUM_PROD_(E, T, R) R(OpSum, SUM, E, T) R(OpProd, PROD, E, T)
+#define MPIR_OPS_MAX_MIN_(E, T, R) R(OpMax, MAX, E, T) R(OpMin, MIN, E, T)
+#define MPIR_OPS_LOGICAL_(E, T, R) R(OpLand, LAND, E, T) R(OpLor, LOR, E, T) R(OpLxor, LXOR, E, T)
+#define MPIR_OPS_LXOR_(E, T, R) R(OpLxor, LXOR, E, T)
+#define MPIR_OPS_BITWISE_(E, T, R) R(OpBand, BAND, E, T) R(OpBor, BOR, E, T) R(OpBxor, BXOR, E, T)
+#define MPIR_OPS_LOC_(E, T, R) R(OpMaxloc, MAXLOC, E, T) R(OpMinloc, MINLOC, E, T)
+// MPI_SUM / MPI_PROD (opsum.c:21-76, opprod.c:21-96): C_INTEGER, FORTRAN_INTEGER,
+// FLOATING_POINT (+EXTRA: char, _Float16), COMPLEX
+#define MPIR_PAIRS_SUM_PROD(R, W) \
+    FOR_INTS(MPIR_OPS_SUM_PROD_, R) FOR_REALS(MPIR_OPS_SUM_PROD_, R) FOR_CPLX(MPIR_OPS_SUM_PROD_, R)
+// MPI_MAX / MPI_MIN (opmax.c:20-55, opmin.c:19-54): integers and reals, no complex
+#define MPIR_PAIRS_MAX_MIN(R, W) FOR_INTS(MPIR_OPS_MAX_MIN_, R) FOR_REALS(MPIR_OPS_MAX_MIN_, R)
+// LAND / LOR (opland.c, oplor.c: integers and _Bool as u8), LXOR (oplxor.c: also
+// the reals, :66-67), BAND / BOR / BXOR (opband.c, opbor.c, opbxor.c: integers and byte)
+#define MPIR_PAIRS_LOGIC(R, W) \
+    FOR_INTS(MPIR_OPS_LOGICAL_, R) FOR_REALS(MPIR_OPS_LXOR_, R) FOR_INTS(MPIR_OPS_BITWISE_, R)
+// MAXLOC / MINLOC on the pair types (opmaxloc.c:79, opminloc.c:78) and the long
+// double rows computed as x87 in software (FLOATING_POINT: SUM, PROD, MAX, MIN,
+// LXOR; its _Complex: SUM, PROD; MPI_LONG_DOUBLE_INT: MAXLOC, MINLOC)
+#define MPIR_PAIRS_PAIRS_X87(R, W) \
+    FOR_PAIRS(MPIR_OPS_LOC_, R) \
+    MPIR_OPS_SUM_PROD_(MPIR_HIP_F80, x80, R) MPIR_OPS_MAX_MIN_(MPIR_HIP_F80, x80, R) MPIR_OPS_LXOR_(MPIR_HIP_F80, x80, R) \
+    W(OpSum, SUM, MPIR_HIP_CF80, cx80, 2) W(OpProd, PROD, MPIR_HIP_CF80, cx80, 1) \
+    W(OpMaxloc, MAXLOC, MPIR_HIP_PLDOUBLEINT, pldint, 2) W(OpMinloc, MINLOC, MPIR_HIP_PLDOUBLEINT, pldint, 2)
+
+// A registration unit: the static constructor that fills one family's table from
+// one list.  MPIR_REG_UNIT(reg, reg_wide, LIST) is the single call's unit;
+// MPIR_REG_FAMILY_UNIT(reg_strided, LIST) a unit of a family with one launcher,
+// which takes the wide pairs as it takes the others (EPL is the wide launcher's
+// alone).  The callbacks handed to the list are a template's name followed by the
+// macro that writes its arguments.
+#define MPIR_REG_R_(Op, OPN, E, T) <Op, T>(MPIR_HIP_OP_##OPN, E);
+#define MPIR_REG_W_(Op, OPN, E, T, EPL) <Op, T, EPL>(MPIR_HIP_OP_##OPN, E);
+#define MPIR_REG_W1_(Op, OPN, E, T, EPL) <Op, T>(MPIR_HIP_OP_##OPN, E);
+#define MPIR_REG_INIT_(R, W, LIST) \
+    namespace {                    \
+    struct Init {                  \
+        Init() { LIST(R, W) }      \
+    } init;                        \
+    }
+#define MPIR_REG_UNIT(narrow, wide, LIST) MPIR_REG_INIT_(narrow MPIR_REG_R_, wide MPIR_REG_W_, LIST)
+#define MPIR_REG_FAMILY_UNIT(family, LIST) MPIR_REG_INIT_(family MPIR_REG_R_, family MPIR_REG_W1_, LIST)

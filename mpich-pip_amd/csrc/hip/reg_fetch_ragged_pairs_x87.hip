@@ -1,24 +1,4 @@
-// reg_fetch_ragged_pairs_x87.hip -- k_reduce_fetch_ragged for reg_pairs_x87.hip's pairs
-// but REPLACE: MAXLOC / MINLOC on the pair types, and the long double rows.
+// reg_fetch_ragged_pairs_x87.hip -- k_reduce_fetch_ragged for the pairs of MPIR_PAIRS_PAIRS_X87 (kernel_table.hpp).
 #include "kernel_table.hpp"
-
 using namespace mpir_hip;
-
-namespace {
-struct Init {
-    Init() {
-#define X(E, T) reg_fetch_ragged<OpMaxloc, T>(MPIR_HIP_OP_MAXLOC, E); reg_fetch_ragged<OpMinloc, T>(MPIR_HIP_OP_MINLOC, E);
-        FOR_PAIRS(X)
-#undef X
-        reg_fetch_ragged<OpSum, x80>(MPIR_HIP_OP_SUM, MPIR_HIP_F80);
-        reg_fetch_ragged<OpProd, x80>(MPIR_HIP_OP_PROD, MPIR_HIP_F80);
-        reg_fetch_ragged<OpMax, x80>(MPIR_HIP_OP_MAX, MPIR_HIP_F80);
-        reg_fetch_ragged<OpMin, x80>(MPIR_HIP_OP_MIN, MPIR_HIP_F80);
-        reg_fetch_ragged<OpLxor, x80>(MPIR_HIP_OP_LXOR, MPIR_HIP_F80);
-        reg_fetch_ragged<OpSum, cx80>(MPIR_HIP_OP_SUM, MPIR_HIP_CF80);
-        reg_fetch_ragged<OpProd, cx80>(MPIR_HIP_OP_PROD, MPIR_HIP_CF80);
-        reg_fetch_ragged<OpMaxloc, pldint>(MPIR_HIP_OP_MAXLOC, MPIR_HIP_PLDOUBLEINT);
-        reg_fetch_ragged<OpMinloc, pldint>(MPIR_HIP_OP_MINLOC, MPIR_HIP_PLDOUBLEINT);
-    }
-} init;
-}  // namespace
+MPIR_REG_FAMILY_UNIT(reg_fetch_ragged, MPIR_PAIRS_PAIRS_X87)

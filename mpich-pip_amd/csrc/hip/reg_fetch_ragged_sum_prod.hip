@@ -1,15 +1,4 @@
-// reg_fetch_ragged_sum_prod.hip -- k_reduce_fetch_ragged for reg_sum_prod.hip's pairs:
-// MPI_SUM / MPI_PROD on integers, reals and complex.
+// reg_fetch_ragged_sum_prod.hip -- k_reduce_fetch_ragged for the pairs of MPIR_PAIRS_SUM_PROD (kernel_table.hpp).
 #include "kernel_table.hpp"
-
 using namespace mpir_hip;
-
-namespace {
-struct Init {
-    Init() {
-#define X(E, T) reg_fetch_ragged<OpSum, T>(MPIR_HIP_OP_SUM, E); reg_fetch_ragged<OpProd, T>(MPIR_HIP_OP_PROD, E);
-        FOR_INTS(X) FOR_REALS(X) FOR_CPLX(X)
-#undef X
-    }
-} init;
-}  // namespace
+MPIR_REG_FAMILY_UNIT(reg_fetch_ragged, MPIR_PAIRS_SUM_PROD)

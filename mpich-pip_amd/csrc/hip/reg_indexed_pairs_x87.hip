@@ -1,24 +1,4 @@
-// reg_indexed_pairs_x87.hip -- k_reduce_indexed for reg_pairs_x87.hip's pairs
-// but REPLACE: MAXLOC / MINLOC on the pair types, and the long double rows.
+// reg_indexed_pairs_x87.hip -- k_reduce_indexed for the pairs of MPIR_PAIRS_PAIRS_X87 (kernel_table.hpp).
 #include "kernel_table.hpp"
-
 using namespace mpir_hip;
-
-namespace {
-struct Init {
-    Init() {
-#define X(E, T) reg_indexed<OpMaxloc, T>(MPIR_HIP_OP_MAXLOC, E); reg_indexed<OpMinloc, T>(MPIR_HIP_OP_MINLOC, E);
-        FOR_PAIRS(X)
-#undef X
-        reg_indexed<OpSum, x80>(MPIR_HIP_OP_SUM, MPIR_HIP_F80);
-        reg_indexed<OpProd, x80>(MPIR_HIP_OP_PROD, MPIR_HIP_F80);
-        reg_indexed<OpMax, x80>(MPIR_HIP_OP_MAX, MPIR_HIP_F80);
-        reg_indexed<OpMin, x80>(MPIR_HIP_OP_MIN, MPIR_HIP_F80);
-        reg_indexed<OpLxor, x80>(MPIR_HIP_OP_LXOR, MPIR_HIP_F80);
-        reg_indexed<OpSum, cx80>(MPIR_HIP_OP_SUM, MPIR_HIP_CF80);
-        reg_indexed<OpProd, cx80>(MPIR_HIP_OP_PROD, MPIR_HIP_CF80);
-        reg_indexed<OpMaxloc, pldint>(MPIR_HIP_OP_MAXLOC, MPIR_HIP_PLDOUBLEINT);
-        reg_indexed<OpMinloc, pldint>(MPIR_HIP_OP_MINLOC, MPIR_HIP_PLDOUBLEINT);
-    }
-} init;
-}  // namespace
+MPIR_REG_FAMILY_UNIT(reg_indexed, MPIR_PAIRS_PAIRS_X87)

@@ -1,15 +1,4 @@
-// reg_ordered_sum_prod.hip -- k_reduce_indexed_ordered for reg_sum_prod.hip's pairs:
-// MPI_SUM / MPI_PROD on integers, reals and complex.
+// reg_ordered_sum_prod.hip -- k_reduce_indexed_ordered for the pairs of MPIR_PAIRS_SUM_PROD (kernel_table.hpp).
 #include "kernel_table.hpp"
-
 using namespace mpir_hip;
-
-namespace {
-struct Init {
-    Init() {
-#define X(E, T) reg_ordered<OpSum, T>(MPIR_HIP_OP_SUM, E); reg_ordered<OpProd, T>(MPIR_HIP_OP_PROD, E);
-        FOR_INTS(X) FOR_REALS(X) FOR_CPLX(X)
-#undef X
-    }
-} init;
-}  // namespace
+MPIR_REG_FAMILY_UNIT(reg_ordered, MPIR_PAIRS_SUM_PROD)

@@ -1,15 +1,4 @@
-// reg_ragged_max_min.hip -- k_reduce_ragged for reg_max_min.hip's pairs:
-// MPI_MAX / MPI_MIN on integers and reals.
+// reg_ragged_max_min.hip -- k_reduce_ragged for the pairs of MPIR_PAIRS_MAX_MIN (kernel_table.hpp).
 #include "kernel_table.hpp"
-
 using namespace mpir_hip;
-
-namespace {
-struct Init {
-    Init() {
-#define X(E, T) reg_ragged<OpMax, T>(MPIR_HIP_OP_MAX, E); reg_ragged<OpMin, T>(MPIR_HIP_OP_MIN, E);
-        FOR_INTS(X) FOR_REALS(X)
-#undef X
-    }
-} init;
-}  // namespace
+MPIR_REG_FAMILY_UNIT(reg_ragged, MPIR_PAIRS_MAX_MIN)

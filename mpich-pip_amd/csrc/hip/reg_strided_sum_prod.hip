@@ -1,15 +1,4 @@
-// reg_strided_sum_prod.hip -- k_reduce_strided for reg_sum_prod.hip's pairs:
-// MPI_SUM / MPI_PROD on integers, reals and complex.
+// reg_strided_sum_prod.hip -- k_reduce_strided for the pairs of MPIR_PAIRS_SUM_PROD (kernel_table.hpp).
 #include "kernel_table.hpp"
-
 using namespace mpir_hip;
-
-namespace {
-struct Init {
-    Init() {
-#define X(E, T) reg_strided<OpSum, T>(MPIR_HIP_OP_SUM, E); reg_strided<OpProd, T>(MPIR_HIP_OP_PROD, E);
-        FOR_INTS(X) FOR_REALS(X) FOR_CPLX(X)
-#undef X
-    }
-} init;
-}  // namespace
+MPIR_REG_FAMILY_UNIT(reg_strided, MPIR_PAIRS_SUM_PROD)
