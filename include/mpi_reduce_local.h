@@ -477,7 +477,9 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_indexed(const void *inbuf, const MPI_Aint
  *       196 at 4 per target, 340 against 840 at 64.  A hot row: all 65,536
  *       blocks of 256 bytes on one target take 29 ms (0.44 us a contribution),
  *       all 4096 of 64 KiB 4.2 ms (1 us): keep such a row out of the table, or
- *       pre-reduce it, where the order of its sum may be chosen.
+ *       pre-reduce it, where the order of its sum may be chosen.  Where only
+ *       determinism is asked of a row's sum, not table order,
+ *       MPIX_Reduce_local_indexed_chunked folds a hot row in chunks of 64.
  *       MPIX_Reduce_local_order: 56 us for 65,536 entries, 31 us for 4096. */
 MPICH_API_PUBLIC int MPIX_Reduce_local_indexed_ordered(const void *inbuf, const MPI_Aint * in_displs,
                               void *inoutbuf, const MPI_Aint * inout_displs, const int *order,
@@ -504,6 +506,88 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_indexed_ordered(const void *inbuf, const 
 MPICH_API_PUBLIC int MPIX_Reduce_local_order_worksize(int nblocks, MPI_Aint * work_bytes);
 MPICH_API_PUBLIC int MPIX_Reduce_local_order(const MPI_Aint * displs, int nblocks, int *order,
                               void *work, MPI_Aint work_bytes, void *hip_stream);
+/* Chunked indexed local reduction: MPIX_Reduce_local_indexed_ordered's operands
+ * and tables for the caller who may choose the order of a row's sum but wants
+ * the same bits every time -- accumulate_ordering=none, gradients (a padding
+ * token's embedding row), assembly (a boundary node): the workloads whose
+ * tables have hot rows.  The contributions of one target are cut into chunks of
+ * MPIX_REDUCE_LOCAL_CHUNK = 64, each chunk is folded on its own, and the
+ * partials are then folded into the target.  Exactly: for one distinct target
+ * displacement d, let its blocks in ascending table number be k_0 < ... <
+ * k_{L-1}, C = 64 and m = ceil(L / C).  Then
+ *   for j = 0 .. m-1:   P_j := a byte copy of input block k_{jC}
+ *     for i = jC+1 .. min((j+1)C, L)-1:
+ *       MPI_Reduce_local(input block k_i, P_j, blocklen, datatype, op)
+ *   for j = 0 .. m-1:   MPI_Reduce_local(P_j, target block at d, blocklen, datatype, op)
+ * bit for bit.  Everything follows from those calls: operand order, the x86 NaN
+ * rule, x87 slot padding, pair padding, integer wrap.  A run of one block is
+ * the indexed call on it; every longer run, short ones included, goes through
+ * its partial, so on floating types this call is NOT the ordered call.  The
+ * association of a row depends on that row's own contributions alone: never on
+ * what other rows receive, on the launch geometry or on the block size.  C is
+ * part of the contract (it fixes the bits), a public constant and not a tuning
+ * knob; 64 was chosen, not measured: it makes the two serial levels equal at
+ * 4096 contributions and is one wave of positions.
+ *   in_off(k), io_off(k), order, the equal-or-disjoint rule for output blocks,
+ *       the residency rules and the validation order are the ordered call's.
+ *   runstart has nblocks ints: runstart[p] is the smallest sorted position q
+ *       with inout_displs[order[q]] == inout_displs[order[p]].  The format is
+ *       public, like order's; MPIX_Reduce_local_runs builds it.
+ *   order and runstart both NULL: MPIX_Reduce_local_indexed unchanged.  Exactly
+ *       one of them NULL, or either given with inout_displs NULL: MPI_ERR_ARG.
+ *   A host runstart (hip_stream NULL) is checked against its definition where
+ *       order and inout_displs are host tables too, otherwise for 0 <=
+ *       runstart[p] <= p (MPI_ERR_ARG); a host order or runstart is read and
+ *       checked before the operands' residency.  A device runstart is not checked and a
+ *       wrong one gives an undefined result; the kernels still clamp what they
+ *       read from it: reads stay inside the tables, writes inside the target
+ *       blocks and work.
+ *   work is device scratch for the partials of runs longer than one chunk, at
+ *       least MPIX_Reduce_local_chunked_worksize(nblocks, blocklen, datatype)
+ *       bytes on the operands' device (fewer work_bytes: MPI_ERR_ARG); no byte
+ *       past that size is touched.  With hip_stream NULL work may be NULL and
+ *       the library uses a buffer of its own; with a stream a NULL work is
+ *       MPI_ERR_BUFFER.  The size depends on its three arguments alone, never
+ *       decreases in nblocks or blocklen, and needs no GPU to ask.
+ *   A call that returns an error has written nothing, in the target or in work.
+ *   Two launches per call (several of each where a launch's workgroup cap asks
+ *       for it), all of the first kernel before any of the second; no workgroup
+ *       waits for another.  With device tables and the caller's work nothing is
+ *       allocated and the call can be captured into a graph: a linear chain.
+ *   Measured: fp32 MPI_SUM against MPIX_Reduce_local_indexed_ordered on the same
+ *       operands, medians of alternated rounds (tools/indexed_chunked_ab.py,
+ *       profiles/indexed_chunked/indexed_chunked_ab.log; DESIGN.md, Chunked
+ *       indexed reductions, has the table).  A hot row: all 65,536 blocks of 256
+ *       bytes on one target take 494 us against the ordered call's 29.1 ms
+ *       (59 x), all 4096 of 64 KiB 345 us against 4.19 ms (12 x).  64 per
+ *       target: 50.8 us against 52.0, and 287 against 341 on 64 KiB blocks.
+ *       Without hot rows the fourth table and the second launch cost: 27.6 us
+ *       against 22.7 with no repeats on 256-byte blocks (1.22 x), 154 against
+ *       143 on 64 KiB blocks (1.08 x); 4 per target 30.3 against 35.7 and 97.9
+ *       against 96.6.  A caller whose tables have no hot rows keeps the indexed
+ *       or the ordered call.  MPIX_Reduce_local_runs: 14 us for 65,536 entries,
+ *       12 us for 4096. */
+#define MPIX_REDUCE_LOCAL_CHUNK 64
+MPICH_API_PUBLIC int MPIX_Reduce_local_indexed_chunked(const void *inbuf, const MPI_Aint * in_displs,
+                              void *inoutbuf, const MPI_Aint * inout_displs, const int *order,
+                              const int *runstart, MPI_Aint disp_unit, int nblocks, int blocklen,
+                              MPI_Datatype datatype, MPI_Op op, void *work, MPI_Aint work_bytes,
+                              void *hip_stream);
+MPICH_API_PUBLIC int MPIX_Reduce_local_chunked_worksize(int nblocks, int blocklen, MPI_Datatype datatype,
+                              MPI_Aint * work_bytes);
+/* The runstart table of MPIX_Reduce_local_indexed_chunked from displs and its
+ * order table.  nblocks < 0: MPI_ERR_COUNT; nblocks 0 succeeds and looks at
+ * nothing; a NULL table: MPI_ERR_ARG.
+ *   All three tables in device memory on one device: one kernel (a lower-bound
+ *       binary search per position), enqueued on the stream or synchronous when
+ *       hip_stream is NULL; no scratch, nothing allocated, and it can be
+ *       captured into a graph.
+ *   A synchronous call also takes any of the tables in host memory (copied
+ *       through the library's table buffer); with all three on the host it is a
+ *       host loop and the GPU runtime is not opened (an order entry out of
+ *       range: MPI_ERR_ARG).  A host table with a stream is MPI_ERR_BUFFER. */
+MPICH_API_PUBLIC int MPIX_Reduce_local_runs(const MPI_Aint * displs, const int *order, int nblocks,
+                              int *runstart, void *hip_stream);
 /* Ragged local reduction: many pieces of unequal length in one launch -- the
  * target of an accumulate on an MPI_Type_indexed / MPI_Type_create_hindexed
  * type, a sub-array with a ragged edge, any list of (location, length) pieces

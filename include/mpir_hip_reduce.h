@@ -56,7 +56,7 @@ enum MPIR_Hip_elem {
 #define MPIR_HIP_ERUNTIME  2   /* HIP runtime failure; see MPIR_Hip_error_string() */
 #define MPIR_HIP_ENOKERNEL 3   /* (op, elem) pair has no kernel */
 #define MPIR_HIP_ENODEV    4   /* no usable GPU */
-#define MPIR_HIP_EARG      5   /* an argument out of range (MPIR_Hip_reduce_strided's strides, MPIR_Hip_reduce_indexed's and MPIR_Hip_reduce_ragged's disp_unit, offsets and tables, MPIR_Hip_reduce_indexed_ordered's order table, MPIR_Hip_order_build's work_bytes) */
+#define MPIR_HIP_EARG      5   /* an argument out of range (MPIR_Hip_reduce_strided's strides, MPIR_Hip_reduce_indexed's and MPIR_Hip_reduce_ragged's disp_unit, offsets and tables, MPIR_Hip_reduce_indexed_ordered's order table, MPIR_Hip_reduce_indexed_chunked's tables and work_bytes, MPIR_Hip_order_build's work_bytes) */
 
 /* Combine inoutbuf[i] = op(inoutbuf[i], inbuf[i]) for i < count elements of
  * class `elem`.  Pointers may be device, pinned-host or pageable-host memory
@@ -354,6 +354,72 @@ int MPIR_Hip_indexed_ordered_plan_info(const void *inbuf, const int64_t *in_disp
 int MPIR_Hip_order_worksize(uint64_t nblocks, uint64_t *work_bytes);
 int MPIR_Hip_order_build(const int64_t *displs, uint64_t nblocks, int *order, void *work, uint64_t work_bytes,
                          void *hip_stream, int sync);
+
+/* Chunked indexed reduction: MPIR_Hip_reduce_indexed_ordered's operands and
+ * tables, but the blocks of one target are not folded one after another: the
+ * run's blocks, in ascending block number, are cut into chunks of
+ * MPIR_HIP_REDUCE_CHUNK counted from the run's first; each chunk is folded into
+ * a partial that starts as a byte copy of the chunk's first input block; the
+ * partials are then combined into the target in order.  The association depends
+ * on the run's own length alone: the same tables and data always give the same
+ * bits, and a hot row's serial depth is 64 + L / 64, not L.  On floating types
+ * the result is NOT the ordered call's.
+ * `runstart` (nblocks ints) is a fourth table: runstart[p] the smallest sorted
+ * position q with io_displs[order[q]] == io_displs[order[p]]
+ * (MPIR_Hip_runs_build makes it).  order and runstart both NULL is
+ * MPIR_Hip_reduce_indexed unchanged; one of them NULL, or either given with
+ * io_displs NULL, MPIR_HIP_EARG.  The argument checks are the ordered call's in
+ * its order, residency too, runstart a fourth table under the same rules --
+ * but the tables are placed first, as the ragged call places them, and a host
+ * order or runstart is read and checked before the operands' residency is.  A
+ * host runstart is checked (MPIR_HIP_EARG): against its definition where order
+ * and io_displs are host tables too, else 0 <= runstart[p] <= p.  A device
+ * runstart is not, and a wrong one gives an undefined result; the kernels clamp
+ * what they read from it, so reads stay inside the tables and writes inside
+ * the target blocks and `work`.
+ * `work`: device scratch for the partials of runs longer than a chunk, at least
+ * MPIR_Hip_chunked_worksize's bytes (2 * ceil(nblocks / 64) slots of the block's
+ * bytes rounded up to 16 plus 16, and 256 to align; from the three arguments
+ * alone, non-decreasing in nblocks and blocklen, no GPU needed; a size past 63
+ * bits: MPIR_HIP_EARG).  work_bytes less: MPIR_HIP_EARG; not device memory on
+ * the operands' device: MPIR_HIP_EBUFFER; bytes past the reported size are never
+ * touched.  work NULL without a stream: the thread's table buffer serves; with
+ * a stream: MPIR_HIP_EBUFFER.
+ * Two kernels (k_chunk_partials, k_fold_partials; reduce_kernels.hpp), each
+ * over the ordered call's plan, every launch of the first before any of the
+ * second: with device tables and the caller's work nothing is allocated and the
+ * call is a linear chain of launches that can be captured into a graph.  A call
+ * that fails has written nothing. */
+#define MPIR_HIP_REDUCE_CHUNK 64
+int MPIR_Hip_chunked_worksize(uint64_t nblocks, uint64_t blocklen, int elem, uint64_t *work_bytes);
+int MPIR_Hip_reduce_indexed_chunked(const void *inbuf, const int64_t *in_displs, void *inoutbuf,
+                                    const int64_t *io_displs, const int *order, const int *runstart,
+                                    uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen, int op, int elem,
+                                    void *work, uint64_t work_bytes, void *hip_stream, int sync);
+
+/* For tests and tools: the launches MPIR_Hip_reduce_indexed_chunked would make
+ * (the tables are only compared with NULL).  out[0..5]: as
+ * MPIR_Hip_indexed_ordered_plan_info reports them, for ONE of the two kernels
+ * (both have the same form, launches and workgroups); out[6] = launches of the
+ * whole call (twice out[1]; with no table the indexed call's); out[7] = the
+ * work bytes.  Returns as that call does, residency apart. */
+int MPIR_Hip_indexed_chunked_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
+                                       const int64_t *io_displs, const int *order, const int *runstart,
+                                       uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen, int op, int elem,
+                                       uint64_t out[8]);
+
+/* The runstart table of a displacement table and its order table: runstart[p] =
+ * the smallest sorted position q with displs[order[q]] == displs[order[p]].
+ * All three device memory on one device: ONE kernel (a lower-bound binary search
+ * per position over displs[order[.]], every order entry clamped) enqueued on
+ * hip_stream, or on the library stream and waited for with sync != 0 and
+ * hip_stream NULL; no scratch, nothing allocated, and it can be captured into a
+ * graph.  In a synchronous call any table may be host memory (with a stream:
+ * MPIR_HIP_EBUFFER): all on the host is a host loop that does not open the GPU
+ * runtime; otherwise the host ones are copied through the table buffer.
+ * nblocks > INT32_MAX: MPIR_HIP_EARG; nblocks 0 succeeds and looks at nothing. */
+int MPIR_Hip_runs_build(const int64_t *displs, const int *order, uint64_t nblocks, int *runstart, void *hip_stream,
+                        int sync);
 
 /* Ragged reduction: npieces pieces of unequal length.  starts (npieces + 1
  * entries) holds the pieces' element offsets in packed order, CSR row pointers:

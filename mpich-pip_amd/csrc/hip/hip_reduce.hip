@@ -37,6 +37,7 @@ BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 OrderedEntry g_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+ChunkedEntry g_chunked[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 RaggedEntry g_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 FetchRaggedEntry g_fetch_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];

@@ -43,6 +43,7 @@ typedef hipError_t (*strided_fn)(const StridedArgs *, uint64_t, hipStream_t);
 typedef hipError_t (*fetch_fn)(const FetchArgs *, hipStream_t);
 typedef hipError_t (*indexed_fn)(const IndexedArgs *, uint64_t, hipStream_t);
 typedef hipError_t (*ordered_fn)(const OrderedArgs *, uint64_t, hipStream_t);
+typedef hipError_t (*chunked_fn)(const ChunkedArgs *, int, uint64_t, hipStream_t);
 typedef hipError_t (*ragged_fn)(const RaggedArgs *, hipStream_t);
 typedef void (*fplan_fn)(const FetchArgs *, FetchPlan *);
 typedef hipError_t (*fetch_ragged_fn)(const FetchRaggedArgs *, hipStream_t);
@@ -85,6 +86,11 @@ struct IndexedEntry { indexed_fn launch; };
 // (MPIR_Hip_reduce_indexed_ordered), for the pairs g_indexed holds
 // (reg_ordered<>, from the reg_ordered_*.hip units).
 struct OrderedEntry { ordered_fn launch; };
+// g_chunked[op][elem], likewise: launch_indexed_chunked<Op, T>, one launch of
+// k_chunk_partials or (fold != 0) k_fold_partials over a range of sorted
+// positions (MPIR_Hip_reduce_indexed_chunked), for the pairs g_ordered holds
+// (reg_chunked<>, from the reg_chunked_*.hip units).
+struct ChunkedEntry { chunked_fn launch; };
 // g_ragged[op][elem], likewise: launch_ragged<Op, T>, the one launch of
 // k_reduce_ragged (MPIR_Hip_reduce_ragged), for the pairs g_indexed holds
 // (reg_ragged<>, from the reg_ragged_*.hip units).
@@ -184,6 +190,7 @@ extern StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern OrderedEntry g_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern ChunkedEntry g_chunked[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern RaggedEntry g_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchRaggedEntry g_fetch_ragged[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchRaggedEntry g_fetch_ragged_bytes[2][kFetchRaggedSizes];
@@ -233,6 +240,11 @@ void reg_indexed(int op, int elem) {
 template <class Op, class T>
 void reg_ordered(int op, int elem) {
     g_ordered[op][elem] = OrderedEntry{&launch_indexed_ordered<Op, T>};
+}
+// the two chunked indexed kernels of the same pairs, from the reg_chunked_*.hip units
+template <class Op, class T>
+void reg_chunked(int op, int elem) {
+    g_chunked[op][elem] = ChunkedEntry{&launch_indexed_chunked<Op, T>};
 }
 // the ragged kernel of the same pairs, from the reg_ragged_*.hip units
 template <class Op, class T>

@@ -6,7 +6,8 @@
 // values' input, so no table of block numbers is written first.  A unit of its
 // own: rocPRIM's headers are the slowest to compile in the library, and nothing
 // else here includes them.  (<rocprim/rocprim.hpp>, the umbrella, is not used:
-// the radix sort's own header is all this needs.)
+// the radix sort's own header is all this needs.)  The kernel behind
+// MPIR_Hip_runs_build sits here too, beside the table it reads.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -21,6 +22,7 @@ namespace mpir_hip {
 size_t order_worksize(uint64_t n);
 hipError_t order_sort(const int64_t *displs, uint64_t n, int *order, void *work, size_t work_bytes, hipStream_t s,
                       size_t *need);
+hipError_t runs_build(const int64_t *displs, const int *order, uint64_t n, int *runstart, hipStream_t s);
 
 namespace {
 constexpr size_t kOrderAlign = 256;
@@ -55,6 +57,39 @@ hipError_t order_sort(const int64_t *displs, uint64_t n, int *order, void *work,
     *need = lead + order_keys_bytes(n) + tmp_bytes;
     if (*need > work_bytes) return hipErrorInvalidValue;
     return rocprim::radix_sort_pairs(tmp, tmp_bytes, displs, keys_out, blocks, order, (size_t)n, 0, 64, s);
+}
+
+
+// The runstart table behind MPIR_Hip_runs_build: runstart[p] = the smallest
+// sorted position q with displs[order[q]] == displs[order[p]].  One kernel, a
+// lane per position: a lower-bound binary search over displs[order[.]] in
+// [0, p], which is non-decreasing where `order` is what it must be.  Every order
+// entry is clamped into [0, n), so a wrong device table gives wrong entries (all
+// in [0, p]) but no read outside the tables.  No scratch, nothing asked of the
+// runtime: the launch can be captured into a graph.
+namespace {
+__global__ __launch_bounds__(256) void k_runs_build(const int64_t *displs, const int *order, uint32_t n, int *runstart) {
+    const uint64_t p = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n) return;
+    auto at = [&](uint32_t q) {
+        const uint32_t k = (uint32_t)order[q];
+        return displs[k < n ? k : n - 1];
+    };
+    const int64_t d = at((uint32_t)p);
+    uint32_t lo = 0, hi = (uint32_t)p;          // the answer is in [lo, hi]
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (at(mid) < d) lo = mid + 1;
+        else hi = mid;
+    }
+    runstart[p] = (int)lo;
+}
+}  // namespace
+
+// Enqueue on `s` the build of runstart[0..n) from displs and order (all device memory), 0 < n <= INT32_MAX
+hipError_t runs_build(const int64_t *displs, const int *order, uint64_t n, int *runstart, hipStream_t s) {
+    hipLaunchKernelGGL(k_runs_build, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, displs, order, (uint32_t)n, runstart);
+    return hipGetLastError();
 }
 
 }  // namespace mpir_hip

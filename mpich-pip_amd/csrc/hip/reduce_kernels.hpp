@@ -1510,6 +1510,374 @@ hipError_t launch_indexed_ordered(const OrderedArgs *a, uint64_t groups, hipStre
 }
 
 // ============================================================================
+// Chunked indexed reductions (MPIR_Hip_reduce_indexed_chunked): the ordered
+// call's tables and run walk, but a run's contributions are cut into chunks of
+// kChunk = 64 counted from the run's first position, each chunk folded into a
+// partial that starts as a byte copy of the chunk's first input block, and the
+// partials then folded into the target in order.  The association is fixed by
+// the run's own length alone, so the bits are deterministic; a hot row's serial
+// depth falls from L to 64 + L / 64.  A fourth table, `runstart` (nblocks ints:
+// the first sorted position of the run position p lies in), tells a position
+// where its chunk starts without a walk back.  Two launches per call, always:
+//
+//   * k_chunk_partials: the ordered plan's units over sorted positions.  A
+//     unit at p works iff (p - runstart[p]) % 64 == 0.  It loads its piece of
+//     input block order[p], walks at most 63 further positions while the
+//     displacement is its own (NARROW_VEC: kOrderedAhead at a time), and then
+//     either -- the run's first chunk, and position p + 64 is not the run's --
+//     loads the target, combines the partial into it and stores, or stores the
+//     partial to its slot of `work`.
+//   * k_fold_partials: a unit at a head (p == runstart[p]) whose run goes on at
+//     p + 64 loads the target, combines the partials of chunks p, p + 64, ...
+//     while the displacement at that position is the head's, and stores once.
+//   * Slots: slot 2 * (q / 64) + (q heads its run) for the chunk at q: a window
+//     of 64 positions starts at most one first chunk and one short last chunk
+//     of runs longer than a chunk.  A slot is slot_bytes apart (the block's
+//     bytes rounded up to 16, and 16 more); the partial sits at the target
+//     block's address mod 16 inside it, so a WIDE workgroup reaches its piece of
+//     every partial through a buffer descriptor as it reaches the target.
+//   * The launch split, the forms, pos0 / nrows and the clamping of `order` are
+//     the ordered kernel's; runstart[p] is clamped to at most p, so a slot index
+//     stays below 2 * ceil(nblocks / 64) whatever a device table holds.
+//
+// No workgroup waits for another: the two kernels are ordered by the stream.
+// No LDS, no scratch, no gridDim.  Tile and vector stores are nt.
+// ============================================================================
+constexpr uint32_t kChunk = MPIR_HIP_REDUCE_CHUNK;
+
+struct ChunkedArgs {
+    OrderedArgs o;              // as for k_reduce_indexed_ordered
+    const int *runstart;        // sorted position -> first sorted position of its run
+    char *work;                 // the partials' slots, 16-byte aligned
+    uint64_t slot_bytes;        // from one slot to the next, a multiple of 16
+};
+
+// what the unit at sorted position p is: its block and displacement, whether p
+// heads its run (first) and whether position p + kChunk is the run's too (cont).
+// True where the unit works in this kernel.
+template <bool Fold>
+__device__ __forceinline__ bool chunk_unit(const ChunkedArgs &a, uint32_t p, uint32_t &k0, int64_t &d0, bool &first,
+                                           bool &cont) {
+    const OrderedArgs &o = a.o;
+    uint32_t rs = (uint32_t)a.runstart[p];
+    if (rs > p) rs = p;
+    const uint32_t p64 = p + kChunk;
+    k0 = ordered_block(o, p);
+    const uint32_t k64 = ordered_block(o, p64 < o.nblocks ? p64 : o.nblocks - 1);
+    d0 = o.io_displs[k0];
+    cont = p64 < o.nblocks && o.io_displs[k64] == d0;
+    first = rs == p;
+    return Fold ? first && cont : (p - rs) % kChunk == 0;
+}
+
+// the partial of the chunk at sorted position q (first: q heads its run) of the target block at io
+__device__ __forceinline__ char *chunk_slot(const ChunkedArgs &a, uint32_t q, bool first, const char *io) {
+    return a.work + (2 * (uint64_t)(q / kChunk) + (first ? 1 : 0)) * a.slot_bytes + (reinterpret_cast<uintptr_t>(io) & 15);
+}
+
+// Element i of the unit at position p, either kernel's work on it
+template <class Op, class T, bool Fold>
+__device__ __forceinline__ void chunk_elem_run(const ChunkedArgs &a, uint32_t p, uint32_t k0, int64_t d0, bool first,
+                                               bool cont, char *io, uint64_t row_bytes, uint64_t i) {
+    const OrderedArgs &o = a.o;
+    Op op;
+    T x, y;
+    if constexpr (Fold) {
+        __builtin_memcpy(&x, io + i * sizeof(T), sizeof(T));
+        for (uint32_t q = p;;) {
+            __builtin_memcpy(&y, chunk_slot(a, q, q == p, io) + i * sizeof(T), sizeof(T));
+            x = op(x, y);
+            q += kChunk;
+            if (q >= o.nblocks || o.io_displs[ordered_block(o, q)] != d0) break;
+        }
+        __builtin_memcpy(io + i * sizeof(T), &x, sizeof(T));
+    } else {
+        __builtin_memcpy(&x, o.in + indexed_off(o.in_displs, k0, o.disp_unit, row_bytes) + i * sizeof(T), sizeof(T));
+        const uint32_t qend = p + kChunk < o.nblocks ? p + kChunk : o.nblocks;
+        for (uint32_t q = p + 1; q < qend; ++q) {
+            const uint32_t k = ordered_block(o, q);
+            if (o.io_displs[k] != d0) break;
+            __builtin_memcpy(&y, o.in + indexed_off(o.in_displs, k, o.disp_unit, row_bytes) + i * sizeof(T), sizeof(T));
+            x = op(x, y);
+        }
+        if (first && !cont) {
+            __builtin_memcpy(&y, io + i * sizeof(T), sizeof(T));
+            y = op(y, x);
+            __builtin_memcpy(io + i * sizeof(T), &y, sizeof(T));
+        } else {
+            __builtin_memcpy(chunk_slot(a, p, first, io) + i * sizeof(T), &x, sizeof(T));
+        }
+    }
+}
+
+// A workgroup's tile (the lane's kVecPerLane vectors at byte offsets wb + u *
+// 1024 of the nrec-byte tile at io_tile) of a block at src: through a descriptor
+// where src shares the target's 16-byte phase, else element by element inside
+// the tile; vectors outside it come back zero.
+template <class T>
+__device__ __forceinline__ void chunk_wide_load(u32x4 (&y)[kVecPerLane], const char *src, const char *io_tile, int nrec,
+                                                int wb) {
+    if (((reinterpret_cast<uintptr_t>(src) ^ reinterpret_cast<uintptr_t>(io_tile)) & 15) == 0) {
+        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)src, 0, nrec, 0x00020000);
+#pragma unroll
+        for (int u = 0; u < kVecPerLane; ++u) y[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, wb + u * 1024, 0, kCachePolicyNT);
+    } else {
+#pragma unroll
+        for (int u = 0; u < kVecPerLane; ++u) {
+            const int off = wb + u * 1024;
+            y[u] = u32x4{0, 0, 0, 0};
+            if ((unsigned)off < (unsigned)nrec) {
+                Pack16<T> e;
+#pragma unroll
+                for (int j = 0; j < (int)(16 / sizeof(T)); ++j)
+                    __builtin_memcpy(&e.e[j], src + off + j * (int)sizeof(T), sizeof(T));
+                y[u] = __builtin_bit_cast(u32x4, e);
+            }
+        }
+    }
+}
+
+template <class Op, class T, bool Fold>
+__device__ __forceinline__ void chunked_wide(const ChunkedArgs &a) {
+    const OrderedArgs &o = a.o;
+    const uint32_t r = blockIdx.x / o.per;
+    if (r >= o.nrows) return;
+    const uint32_t p = o.pos0 + r;
+    const uint64_t tile = blockIdx.x - r * o.per;
+    const uint64_t row_bytes = o.blocklen * sizeof(T);
+    uint32_t k0;
+    int64_t d0;
+    bool first, cont;
+    if (!chunk_unit<Fold>(a, p, k0, d0, first, cont)) return;
+    k0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)k0);
+    d0 = (int64_t)wave_uniform64((uint64_t)d0);
+    char *io = o.io + (uint64_t)d0 * o.disp_unit;
+    // the target's own split, as in the ordered kernel: a workgroup owns the same
+    // piece of the target, of every input block and of every partial
+    const SegSplit s = seg_split<T>(io, io, o.blocklen);
+    if (tile >= batch_seg_groups<T>(s, io, o.blocklen)) return;
+    const uint32_t qend = p + kChunk < o.nblocks ? p + kChunk : o.nblocks;
+    if constexpr (sizeof(T) <= 16) {
+        if (s.tile) {
+            char *iov = io + s.head_bytes;
+            const int64_t start = (int64_t)(tile * kTileBytes) - (int64_t)tile_shift(iov);
+            const uint64_t lo = start > 0 ? (uint64_t)start : 0;
+            if (lo < s.vbytes) {
+                const uint64_t end = (uint64_t)(start + kTileBytes);
+                const int nrec = (int)((end < s.vbytes ? end : s.vbytes) - lo);
+                const int cut = (int)(lo - start);
+                const uint64_t at = s.head_bytes + lo;          // the tile's place in a block
+                __amdgpu_buffer_rsrc_t rio = __builtin_amdgcn_make_buffer_rsrc((void *)(iov + lo), 0, nrec, 0x00020000);
+                const int t = (int)threadIdx.x;
+                const int wb = (t >> 6) * (kVecPerLane * 1024) + (t & 63) * 16 - cut;
+                u32x4 x[kVecPerLane], y[kVecPerLane];
+                if constexpr (Fold) {
+#pragma unroll
+                    for (int u = 0; u < kVecPerLane; ++u)
+                        x[u] = __builtin_amdgcn_raw_buffer_load_b128(rio, wb + u * 1024, 0, kCachePolicyNT);
+                    for (uint32_t q = p;;) {
+                        chunk_wide_load<T>(y, chunk_slot(a, q, q == p, io) + at, iov + lo, nrec, wb);
+#pragma unroll
+                        for (int u = 0; u < kVecPerLane; ++u) x[u] = combine16<Op, T>(x[u], y[u]);
+                        q += kChunk;
+                        if (q >= o.nblocks) break;
+                        const uint32_t k = (uint32_t)__builtin_amdgcn_readfirstlane((int)ordered_block(o, q));
+                        if (o.io_displs[k] != d0) break;
+                    }
+#pragma unroll
+                    for (int u = 0; u < kVecPerLane; ++u) store16(x[u], rio, wb + u * 1024, false);
+                } else {
+                    chunk_wide_load<T>(x, o.in + wave_uniform64(indexed_off(o.in_displs, k0, o.disp_unit, row_bytes)) + at,
+                                       iov + lo, nrec, wb);
+                    for (uint32_t q = p + 1; q < qend; ++q) {
+                        const uint32_t k = (uint32_t)__builtin_amdgcn_readfirstlane((int)ordered_block(o, q));
+                        if (o.io_displs[k] != d0) break;
+                        chunk_wide_load<T>(y, o.in + wave_uniform64(indexed_off(o.in_displs, k, o.disp_unit, row_bytes)) + at,
+                                           iov + lo, nrec, wb);
+#pragma unroll
+                        for (int u = 0; u < kVecPerLane; ++u) x[u] = combine16<Op, T>(x[u], y[u]);
+                    }
+                    if (first && !cont) {
+#pragma unroll
+                        for (int u = 0; u < kVecPerLane; ++u)
+                            y[u] = __builtin_amdgcn_raw_buffer_load_b128(rio, wb + u * 1024, 0, kCachePolicyNT);
+#pragma unroll
+                        for (int u = 0; u < kVecPerLane; ++u) store16(combine16<Op, T>(y[u], x[u]), rio, wb + u * 1024, false);
+                    } else {
+                        __amdgpu_buffer_rsrc_t rw =
+                            __builtin_amdgcn_make_buffer_rsrc((void *)(chunk_slot(a, p, first, io) + at), 0, nrec, 0x00020000);
+#pragma unroll
+                        for (int u = 0; u < kVecPerLane; ++u) store16(x[u], rw, wb + u * 1024, false);
+                    }
+                }
+            }
+            if (tile == 0) {
+                // the head and tail elements, a lane each as in reduce_seg
+                const unsigned t = threadIdx.x;
+                if (t < s.nhead) chunk_elem_run<Op, T, Fold>(a, p, k0, d0, first, cont, io, row_bytes, t);
+                else if (t >= 64 && t - 64 < s.ntail)
+                    chunk_elem_run<Op, T, Fold>(a, p, k0, d0, first, cont, io, row_bytes,
+                                                (s.head_bytes + s.vbytes) / sizeof(T) + (t - 64));
+            }
+            return;
+        }
+    }
+    constexpr uint64_t per = kTileBytes / sizeof(T);
+    const uint64_t base = tile * per;
+    const uint64_t end = base + per < o.blocklen ? base + per : o.blocklen;
+    for (uint64_t i = base + threadIdx.x; i < end; i += kThreads)
+        chunk_elem_run<Op, T, Fold>(a, p, k0, d0, first, cont, io, row_bytes, i);
+}
+
+template <class Op, class T, bool Fold>
+__device__ __forceinline__ void chunked_narrow(const ChunkedArgs &a) {
+    const OrderedArgs &o = a.o;
+    const uint32_t upr = o.per;                             // units per block
+    const uint64_t row_bytes = o.blocklen * sizeof(T);
+    const unsigned t = threadIdx.x;
+    if constexpr (sizeof(T) <= 16) {
+        if (o.form == MPIR_HIP_INDEXED_NARROW_VEC) {
+            constexpr uint32_t upw = strided_units_per_group<T>(true);
+            constexpr int per_lane = (int)(upw / kThreads);
+            const uint64_t u0 = (uint64_t)blockIdx.x * upw;
+            const uint64_t row0 = u0 / upr;
+            const uint32_t col0 = (uint32_t)(u0 - row0 * upr);
+            // a unit past the launch's last position is clamped into it, as in the ordered kernel
+            const uint64_t last = o.nrows - 1;
+            uint32_t pos[per_lane], rs[per_lane], k[per_lane], k64[per_lane];
+            uint64_t off[per_lane];
+            int64_t d[per_lane], d64[per_lane];
+            bool act[per_lane], first[per_lane], cont[per_lane];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                const uint32_t c = col0 + t + (uint32_t)j * kThreads;
+                const uint32_t q = c / upr;
+                const uint64_t r = row0 + q;
+                act[j] = r <= last;
+                pos[j] = o.pos0 + (uint32_t)(act[j] ? r : last);
+                off[j] = (uint64_t)(c - q * upr) * 16;
+            }
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) rs[j] = (uint32_t)a.runstart[pos[j]];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) k[j] = ordered_block(o, pos[j]);
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j)
+                k64[j] = ordered_block(o, pos[j] + kChunk < o.nblocks ? pos[j] + kChunk : o.nblocks - 1);
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) d[j] = o.io_displs[k[j]];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) d64[j] = o.io_displs[k64[j]];
+            u32x4 x[per_lane];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                if (rs[j] > pos[j]) rs[j] = pos[j];
+                first[j] = rs[j] == pos[j];
+                cont[j] = pos[j] + kChunk < o.nblocks && d64[j] == d[j];
+                act[j] = act[j] && (Fold ? first[j] && cont[j] : (pos[j] - rs[j]) % kChunk == 0);
+                x[j] = u32x4{0, 0, 0, 0};
+                // only working units touch data: the target's vector (the fold), or
+                // the chunk's first input block's
+                if (act[j]) {
+                    const char *src = Fold ? o.io + (uint64_t)d[j] * o.disp_unit
+                                           : o.in + indexed_off(o.in_displs, k[j], o.disp_unit, row_bytes);
+                    x[j] = __builtin_nontemporal_load((const global_u32x4 *)(src + off[j]));
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                if (!act[j]) continue;
+                char *io = o.io + (uint64_t)d[j] * o.disp_unit;
+                u32x4 v = x[j];
+                // the sources that follow, kOrderedAhead at a time as the ordered kernel
+                // looks ahead: positions p + 1 .. p + 63 and their input blocks, or (the
+                // fold) positions p, p + 64, ... and their partials
+                const uint32_t step = Fold ? kChunk : 1;
+                const uint32_t qend = Fold || pos[j] + kChunk >= o.nblocks ? o.nblocks : pos[j] + kChunk;
+                bool more = true;
+                for (uint32_t q = Fold ? pos[j] : pos[j] + 1; more && q < qend; q += kOrderedAhead * step) {
+                    uint32_t kq[kOrderedAhead];
+                    int64_t dq[kOrderedAhead];
+                    u32x4 w[kOrderedAhead];
+                    bool in_run[kOrderedAhead];
+#pragma unroll
+                    for (int i = 0; i < kOrderedAhead; ++i)
+                        kq[i] = ordered_block(o, q + i * step < o.nblocks ? q + i * step : o.nblocks - 1);
+#pragma unroll
+                    for (int i = 0; i < kOrderedAhead; ++i) dq[i] = o.io_displs[kq[i]];
+#pragma unroll
+                    for (int i = 0; i < kOrderedAhead; ++i) {
+                        const uint32_t qi = q + i * step;
+                        more = more && qi < qend && dq[i] == d[j];
+                        w[i] = u32x4{0, 0, 0, 0};
+                        if (more) {
+                            const char *src = Fold ? chunk_slot(a, qi, qi == pos[j], io)
+                                                   : o.in + indexed_off(o.in_displs, kq[i], o.disp_unit, row_bytes);
+                            w[i] = __builtin_nontemporal_load((const global_u32x4 *)(src + off[j]));
+                        }
+                        in_run[i] = more;
+                    }
+#pragma unroll
+                    for (int i = 0; i < kOrderedAhead; ++i)
+                        if (in_run[i]) v = combine16<Op, T>(v, w[i]);
+                }
+                if (Fold) {
+                    __builtin_nontemporal_store(v, (global_u32x4 *)(io + off[j]));
+                } else if (first[j] && !cont[j]) {
+                    const u32x4 tg = __builtin_nontemporal_load((const global_u32x4 *)(io + off[j]));
+                    __builtin_nontemporal_store(combine16<Op, T>(tg, v), (global_u32x4 *)(io + off[j]));
+                } else {
+                    __builtin_nontemporal_store(v, (global_u32x4 *)(chunk_slot(a, pos[j], first[j], io) + off[j]));
+                }
+            }
+            return;
+        }
+    }
+    constexpr uint32_t upw = strided_units_per_group<T>(false);
+    const uint64_t u0 = (uint64_t)blockIdx.x * upw;
+    const uint64_t row0 = u0 / upr;
+    const uint32_t col0 = (uint32_t)(u0 - row0 * upr);
+    for (uint32_t u = t; u < upw; u += kThreads) {
+        const uint32_t c = col0 + u;
+        const uint32_t q = c / upr;
+        const uint64_t r = row0 + q;
+        if (r >= o.nrows) break;                            // positions only grow with u
+        const uint32_t p = o.pos0 + (uint32_t)r;
+        uint32_t k0;
+        int64_t d0;
+        bool first, cont;
+        if (!chunk_unit<Fold>(a, p, k0, d0, first, cont)) continue;
+        chunk_elem_run<Op, T, Fold>(a, p, k0, d0, first, cont, o.io + (uint64_t)d0 * o.disp_unit, row_bytes, c - q * upr);
+    }
+}
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_chunk_partials(ChunkedArgs a) {
+    if (a.o.form == MPIR_HIP_INDEXED_WIDE) chunked_wide<Op, T, false>(a);
+    else chunked_narrow<Op, T, false>(a);
+}
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_fold_partials(ChunkedArgs a) {
+    if (a.o.form == MPIR_HIP_INDEXED_WIDE) chunked_wide<Op, T, true>(a);
+    else chunked_narrow<Op, T, true>(a);
+}
+
+// one launch of either kernel (fold: k_fold_partials): `groups` workgroups over
+// sorted positions [pos0, pos0 + nrows)
+template <class Op, class T>
+hipError_t launch_indexed_chunked(const ChunkedArgs *a, int fold, uint64_t groups, hipStream_t s) {
+    const OrderedArgs &o = a->o;
+    if (!o.nrows || !o.per || !o.blocklen || !o.disp_unit || !o.io_displs || !o.order || !a->runstart || !a->work ||
+        (reinterpret_cast<uintptr_t>(a->work) & 15) || (a->slot_bytes & 15) || a->slot_bytes < o.blocklen * sizeof(T) + 16 ||
+        (uint64_t)o.pos0 + o.nrows > o.nblocks || groups < 1 || groups > kBatchMaxGroups)
+        return hipErrorInvalidValue;
+    if (fold) hipLaunchKernelGGL((k_fold_partials<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
+    else hipLaunchKernelGGL((k_chunk_partials<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+// ============================================================================
 // Fetching ordered indexed reductions (MPIR_Hip_reduce_fetch_indexed_ordered):
 // the ordered kernel with every intermediate value of a run handed out.  The
 // call is MPIX_Reduce_local_fetch block by block in table order: block k of the

@@ -1,0 +1,4 @@
+// reg_chunked_max_min.hip -- k_chunk_partials and k_fold_partials for the pairs of MPIR_PAIRS_MAX_MIN (kernel_table.hpp).
+#include "kernel_table.hpp"
+using namespace mpir_hip;
+MPIR_REG_FAMILY_UNIT(reg_chunked, MPIR_PAIRS_MAX_MIN)

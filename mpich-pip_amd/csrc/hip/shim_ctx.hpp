@@ -34,6 +34,7 @@ void direct_placement(int dev, int out[5]);
 size_t order_worksize(uint64_t n);
 hipError_t order_sort(const int64_t *displs, uint64_t n, int *order, void *work, size_t work_bytes, hipStream_t s,
                       size_t *need);
+hipError_t runs_build(const int64_t *displs, const int *order, uint64_t n, int *runstart, hipStream_t s);
 
 // hip_reduce.hip, for table_calls.hip (the library does not export them): an
 // element class's bytes, the range check of (op, elem), and a synchronous call's wait

@@ -1,7 +1,7 @@
 // table_calls.hip -- the shim's calls on many blocks at once: MPIR_Hip_reduce_batch,
-// _strided, _fetch, _indexed, _indexed_ordered, _ragged, _fetch_ragged,
-// _fetch_indexed_ordered, MPIR_Hip_cas_indexed_ordered and MPIR_Hip_order_build,
-// with their *_plan_info functions.  Every one settles residency before it
+// _strided, _fetch, _indexed, _indexed_ordered, _indexed_chunked, _ragged,
+// _fetch_ragged, _fetch_indexed_ordered, MPIR_Hip_cas_indexed_ordered,
+// MPIR_Hip_order_build and MPIR_Hip_runs_build, with their *_plan_info functions.  Every one settles residency before it
 // enqueues (a call that fails has written nothing) and then runs on one call
 // frame: the steps below, which each entry point calls in its own order -- that
 // order decides which error a caller sees (tests/test_table_call_precedence_gpu.py).
@@ -475,6 +475,61 @@ int ordered_host_order(const int *order, const int64_t *io_displs, uint64_t nblo
             if (a > b || (a == b && order[p - 1] > order[p])) return MPIR_HIP_EARG;
         }
     return MPIR_HIP_OK;
+}
+
+// ---- chunked indexed calls: the ordered call's plan, twice.
+// the argument checks MPIR_Hip_reduce_indexed_chunked makes before it looks at
+// a pointer, for a call with its two tables: the ordered call's in its order
+int chunked_args(const void *in_displs, const void *io_displs, uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen,
+                 int op, int elem, int *form) {
+    if (!pair_in_range(op, elem) || !g_chunked[op][elem].launch) return MPIR_HIP_ENOKERNEL;
+    return ordered_args(in_displs, io_displs, disp_unit, nblocks, blocklen, op, elem, form);
+}
+
+// from one partial's slot to the next: the block's bytes rounded up to 16, and
+// 16 for the target's address mod 16 (reduce_kernels.hpp, chunk_slot)
+uint64_t chunked_slot_bytes(uint64_t row_bytes) { return ((row_bytes + 15) & ~(uint64_t)15) + 16; }
+
+constexpr uint64_t kChunkedAlign = 256;
+
+// the work of a chunked call: room to align the caller's pointer and two slots
+// per window of kChunk sorted positions.  False where it passes 63 bits.
+bool chunked_worksize(uint64_t nblocks, uint64_t blocklen, int elem, uint64_t *bytes) {
+    const uint64_t esz = g_elem_size[elem], top = ~(uint64_t)0 >> 1;
+    if (blocklen > (top - 64) / esz) return false;
+    const uint64_t slot = chunked_slot_bytes(blocklen * esz), slots = 2 * ((nblocks + kChunk - 1) / kChunk);
+    if (slots && slot > (top - kChunkedAlign) / slots) return false;
+    *bytes = kChunkedAlign + slots * slot;
+    return true;
+}
+
+// A host runstart table, read before anything is enqueued: against its
+// definition where the order and output tables are host memory too (else
+// null), otherwise 0 <= runstart[p] <= p.  MPIR_HIP_EARG otherwise.
+int chunked_host_runs(const int *runstart, const int *order, const int64_t *io_displs, uint64_t nblocks) {
+    int head = 0;
+    for (uint64_t p = 0; p < nblocks; ++p) {
+        if (runstart[p] < 0 || (uint64_t)runstart[p] > p) return MPIR_HIP_EARG;
+        if (!order || !io_displs) continue;
+        if (!p || io_displs[order[p - 1]] != io_displs[order[p]]) head = (int)p;   // (order: checked before)
+        if (runstart[p] != head) return MPIR_HIP_EARG;
+    }
+    return MPIR_HIP_OK;
+}
+
+// The launches of a chunked plan: ordered_launches with k_chunk_partials, then
+// again with k_fold_partials -- every launch of the first before any of the second.
+template <class F>
+void chunked_launches(const StridedPlan &p, const void *in, const int64_t *in_displs, void *io, const int64_t *io_displs,
+                      const int *order, const int *runstart, uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen,
+                      char *work, F emit) {
+    bool go = true;
+    for (int fold = 0; fold < 2 && go; ++fold)
+        ordered_launches(p, in, in_displs, io, io_displs, order, disp_unit, nblocks, blocklen,
+                         [&](const OrderedArgs &o, uint64_t groups) {
+                             const ChunkedArgs a{o, runstart, work, chunked_slot_bytes(p.row_bytes)};
+                             return go = emit(a, fold, groups);
+                         });
 }
 
 // ---- ragged calls: unequal pieces from a table of packed element offsets.
@@ -1012,6 +1067,145 @@ int MPIR_Hip_order_build(const int64_t *displs, uint64_t nblocks, int *order, vo
         snprintf(ctx().err, sizeof(ctx().err), "the order sort needs %zu bytes of work, MPIR_Hip_order_worksize gave %zu",
                  wants, need);
     return rc;
+}
+
+int MPIR_Hip_chunked_worksize(uint64_t nblocks, uint64_t blocklen, int elem, uint64_t *work_bytes) {
+    if (elem <= 0 || elem >= MPIR_HIP_NELEMS) return MPIR_HIP_ENOKERNEL;
+    if (nblocks > (uint64_t)INT32_MAX || !chunked_worksize(nblocks, blocklen, elem, work_bytes)) return MPIR_HIP_EARG;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_indexed_chunked_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,
+                                       const int64_t *io_displs, const int *order, const int *runstart,
+                                       uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen, int op, int elem,
+                                       uint64_t out[8]) {
+    if (!pair_in_range(op, elem) || !g_chunked[op][elem].launch) return MPIR_HIP_ENOKERNEL;
+    if (!order && !runstart) {
+        const int rc = MPIR_Hip_indexed_plan_info(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, op,
+                                                  elem, out);
+        if (rc == MPIR_HIP_OK) {
+            out[6] = out[1];
+            out[7] = 0;
+        }
+        return rc;
+    }
+    int form = 0;
+    const int rc = chunked_args(in_displs, io_displs, disp_unit, nblocks, blocklen, op, elem, &form);
+    if (rc != MPIR_HIP_OK) return rc;
+    for (int k = 0; k < 8; ++k) out[k] = 0;
+    out[0] = (uint64_t)form;
+    out[4] = mpir_hip::g_strided_wide.load(std::memory_order_relaxed);
+    if (form == MPIR_HIP_INDEXED_EMPTY) return MPIR_HIP_OK;
+    if (!order || !runstart) return MPIR_HIP_EARG;
+    if (!chunked_worksize(nblocks, blocklen, elem, &out[7])) return MPIR_HIP_EARG;
+    StridedPlan p;
+    indexed_plan(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, elem, p);
+    plan_out(p, out, 5);
+    out[6] = 2 * p.launches;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_reduce_indexed_chunked(const void *inbuf, const int64_t *in_displs, void *inoutbuf,
+                                    const int64_t *io_displs, const int *order, const int *runstart,
+                                    uint64_t disp_unit, uint64_t nblocks, uint64_t blocklen, int op, int elem,
+                                    void *work, uint64_t work_bytes, void *hip_stream, int sync) {
+    if (!pair_in_range(op, elem) || !g_chunked[op][elem].launch) return MPIR_HIP_ENOKERNEL;
+    // neither table: a promise of no repeats, the indexed call unchanged
+    if (!order && !runstart)
+        return MPIR_Hip_reduce_indexed(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, op, elem,
+                                       hip_stream, sync);
+    int form = 0;
+    int rc = chunked_args(in_displs, io_displs, disp_unit, nblocks, blocklen, op, elem, &form);
+    if (rc != MPIR_HIP_OK || form == MPIR_HIP_INDEXED_EMPTY) return rc;
+    uint64_t need = 0;
+    if (!order || !runstart || !chunked_worksize(nblocks, blocklen, elem, &need) || (work && work_bytes < need))
+        return MPIR_HIP_EARG;
+    ctx().err[0] = 0;
+    // Everything is settled before anything is enqueued (a call that fails has
+    // written nothing), tables first as the ragged call settles them: each is
+    // device memory on any device or, in a synchronous call on the library
+    // stream, host memory, and a host order or runstart is then read for what is
+    // wrong with it whatever the operands are (MPIR_HIP_EARG).  Then residency
+    // as the ordered call's: both bases, the last byte of a packed input, the
+    // device tables on the operands' device, a host displacement table's
+    // extremes, and the work.
+    const uint64_t row_bytes = blocklen * g_elem_size[elem], bytes = nblocks * row_bytes;
+    const char *base[2] = {static_cast<const char *>(inbuf), static_cast<char *>(inoutbuf)};
+    Table t[4] = {{in_displs, (size_t)nblocks * sizeof(int64_t)}, {io_displs, (size_t)nblocks * sizeof(int64_t)},
+                  {order, (size_t)nblocks * sizeof(int)}, {runstart, (size_t)nblocks * sizeof(int)}};
+    for (int k = 0; k < 4; ++k)
+        if (t[k].p && (rc = place_table(t[k], -1, hip_stream, sync)) != MPIR_HIP_OK) return rc;
+    if (t[2].host && (rc = ordered_host_order(order, t[1].host ? io_displs : nullptr, nblocks)) != MPIR_HIP_OK) return rc;
+    if (t[3].host &&
+        (rc = chunked_host_runs(runstart, t[1].host && t[2].host ? order : nullptr, io_displs, nblocks)) != MPIR_HIP_OK)
+        return rc;
+    Residency r;
+    if (!r.operand(0, base[0], in_displs ? 0 : bytes) || !r.operand(1, base[1])) return MPIR_HIP_EBUFFER;
+    for (int k = 0; k < 4; ++k) {
+        if (!t[k].p) continue;
+        if (!t[k].host && t[k].dev != r.dev) return MPIR_HIP_EBUFFER;
+        if (t[k].host && k < 2 &&
+            (rc = indexed_host_table(base[k], t[k].as<int64_t>(), disp_unit, nblocks, row_bytes, r.dev)) != MPIR_HIP_OK)
+            return rc;
+    }
+    Table tw{work, (size_t)need};
+    if (work ? place_table(tw, r.dev, nullptr, 0) != MPIR_HIP_OK : hip_stream != nullptr) return MPIR_HIP_EBUFFER;
+    StridedPlan p;
+    indexed_plan(inbuf, in_displs, inoutbuf, io_displs, disp_unit, nblocks, blocklen, elem, p);
+    if ((rc = plan_fits(p, "an indexed block needs more workgroups than one launch holds")) != MPIR_HIP_OK) return rc;
+    Frame f(r.dev, hip_stream, sync);
+    if ((rc = f.open()) != MPIR_HIP_OK) return rc;
+    // (no work given: the thread's table buffer, behind the host tables' copies)
+    char *rest = nullptr;
+    if ((rc = stage_tables(f, t, 4, "chunked indexed table copy", work ? 0 : need, &rest)) != MPIR_HIP_OK) return rc;
+    // (never past the reported size, whatever the caller's buffer holds beyond it)
+    char *w = work ? reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(work) + kChunkedAlign - 1) & ~(uintptr_t)(kChunkedAlign - 1))
+                   : rest;
+    hipError_t e = hipSuccess;
+    const chunked_fn launch = g_chunked[op][elem].launch;
+    chunked_launches(p, inbuf, t[0].as<int64_t>(), inoutbuf, t[1].as<int64_t>(), t[2].as<int>(), t[3].as<int>(), disp_unit,
+                     nblocks, blocklen, w, [&](const ChunkedArgs &a, int fold, uint64_t groups) {
+                         e = launch(&a, fold, groups, f.s);
+                         return e == hipSuccess;
+                     });
+    return f.close(e, "chunked indexed launch");
+}
+
+int MPIR_Hip_runs_build(const int64_t *displs, const int *order, uint64_t nblocks, int *runstart, void *hip_stream,
+                        int sync) {
+    if (nblocks > (uint64_t)INT32_MAX) return MPIR_HIP_EARG;
+    if (!nblocks) return MPIR_HIP_OK;
+    ctx().err[0] = 0;
+    // the three tables, each device memory on the one device or (synchronously on
+    // the library stream) host memory; every refusal here is MPIR_HIP_EBUFFER
+    Table t[3] = {{displs, (size_t)nblocks * sizeof(int64_t)}, {order, (size_t)nblocks * sizeof(int)},
+                  {runstart, (size_t)nblocks * sizeof(int)}};
+    int dev = -1;
+    for (int k = 0; k < 3; ++k) {
+        if (place_table(t[k], dev, hip_stream, sync) != MPIR_HIP_OK) return MPIR_HIP_EBUFFER;
+        if (!t[k].host) dev = t[k].dev;
+    }
+    if (t[0].host && t[1].host && t[2].host) {
+        // all on the host: a host loop, no GPU runtime needed (an order entry out
+        // of range: MPIR_HIP_EARG, nothing written)
+        for (uint64_t p = 0; p < nblocks; ++p)
+            if (order[p] < 0 || (uint64_t)order[p] >= nblocks) return MPIR_HIP_EARG;
+        for (uint64_t p = 0; p < nblocks; ++p)
+            runstart[p] = p && displs[order[p - 1]] == displs[order[p]] ? runstart[p - 1] : (int)p;
+        return MPIR_HIP_OK;
+    }
+    Frame f(dev, hip_stream, sync);
+    int rc = f.open();
+    if (rc != MPIR_HIP_OK) return rc;
+    // a host runstart's device side comes from the thread's table buffer, behind
+    // the host inputs' copies (a synchronous call: done with it on return)
+    const bool rhost = t[2].host;
+    char *rest = nullptr;
+    if ((rc = stage_tables(f, t, 2, "runs build table copy", rhost ? t[2].bytes : 0, &rest)) != MPIR_HIP_OK) return rc;
+    int *d_runs = rhost ? reinterpret_cast<int *>(rest) : runstart;
+    hipError_t e = runs_build(t[0].as<int64_t>(), t[1].as<int>(), nblocks, d_runs, f.s);
+    if (e == hipSuccess && rhost) e = hipMemcpyAsync(runstart, d_runs, t[2].bytes, hipMemcpyDeviceToHost, f.s);
+    return f.close(e, "runs build");
 }
 
 int MPIR_Hip_ragged_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,

@@ -820,6 +820,136 @@ int MPIX_Reduce_local_order(const MPI_Aint * displs, int nblocks, int *order, vo
     CS_RETURN(reduce_local_order(displs, nblocks, order, work, work_bytes, hip_stream));
 }
 
+/* ---- MPIX_Reduce_local_indexed_chunked: hot rows folded in chunks of 64 (see the header) */
+#pragma weak MPIR_Hip_reduce_indexed_chunked
+#pragma weak MPIR_Hip_chunked_worksize
+#pragma weak MPIR_Hip_runs_build
+static int reduce_local_indexed_chunked(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                                        const MPI_Aint * inout_displs, const int *order, const int *runstart,
+                                        MPI_Aint disp_unit, int nblocks, int blocklen, MPI_Datatype datatype,
+                                        MPI_Op op, void *work, MPI_Aint work_bytes, void *hip_stream)
+{
+    static const char *fc = "MPIX_Reduce_local_indexed_chunked";
+    int mpi_errno, opidx, elem, rc;
+    uint64_t need = 0;
+    const int empty = nblocks == 0 || blocklen == 0;
+    _Static_assert(MPIX_REDUCE_LOCAL_CHUNK == MPIR_HIP_REDUCE_CHUNK, "the public chunk length is the kernels'");
+    if (nblocks < 0 || blocklen < 0) {
+        MPIR_Err_set_detail("negative %s %d", nblocks < 0 ? "nblocks" : "blocklen", nblocks < 0 ? nblocks : blocklen);
+        return err_return(fc, MPI_ERR_COUNT);
+    }
+    /* the ordered call's order: an empty call's pointers are not looked at (the
+     * op still is) */
+    mpi_errno = empty ? validate(NULL, NULL, 0, datatype, op) : validate(inbuf, inoutbuf, blocklen, datatype, op);
+    if (mpi_errno != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
+    if (disp_unit <= 0) {
+        MPIR_Err_set_detail("disp_unit %ld is not positive", (long) disp_unit);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (empty)
+        return MPI_SUCCESS;
+    if (order == NULL || runstart == NULL) {
+        MPIR_Err_set_detail("%s is NULL and %s is not: the two tables come together", order == NULL ? "order" : "runstart",
+                            order == NULL ? "runstart" : "order");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (inout_displs == NULL) {
+        MPIR_Err_set_detail("order and runstart with no inout_displs: a packed target has no repeats to fold");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (work != NULL && work_bytes < 0) {
+        MPIR_Err_set_detail("negative work_bytes %ld", (long) work_bytes);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if ((mpi_errno = builtin_op_elem(datatype, op, &opidx, &elem)) != MPI_SUCCESS ||
+        (mpi_errno = shim_has(MPIR_Hip_reduce_indexed_chunked != NULL && MPIR_Hip_chunked_worksize != NULL,
+                              "MPIR_Hip_reduce_indexed_chunked")) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
+    if (work != NULL && MPIR_Hip_chunked_worksize((uint64_t) nblocks, (uint64_t) blocklen, elem, &need) == MPIR_HIP_OK &&
+        (uint64_t) work_bytes < need) {
+        MPIR_Err_set_detail("%s: work_bytes %ld is less than MPIX_Reduce_local_chunked_worksize reports", fc,
+                            (long) work_bytes);
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    rc = MPIR_Hip_reduce_indexed_chunked(inbuf, (const int64_t *) in_displs, inoutbuf, (const int64_t *) inout_displs,
+                                         order, runstart, (uint64_t) disp_unit, (uint64_t) nblocks, (uint64_t) blocklen,
+                                         opidx, elem, work, (uint64_t) work_bytes, hip_stream, hip_stream == NULL);
+    return shim_result(fc, rc, "%s needs device-resident operands on one device, and its tables and work there too "
+                       "(host tables, or no work: the synchronous call only)",
+                       "%s: a block's offset does not fit the address space, the order table is not a stable sort of "
+                       "inout_displs, or the runstart table is not the first positions of its runs");
+}
+
+int MPIX_Reduce_local_indexed_chunked(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,
+                                      const MPI_Aint * inout_displs, const int *order, const int *runstart,
+                                      MPI_Aint disp_unit, int nblocks, int blocklen, MPI_Datatype datatype, MPI_Op op,
+                                      void *work, MPI_Aint work_bytes, void *hip_stream)
+{
+    /* neither table: the indexed call unchanged, its own name on the error stack */
+    if (order == NULL && runstart == NULL)
+        return MPIX_Reduce_local_indexed(inbuf, in_displs, inoutbuf, inout_displs, disp_unit, nblocks, blocklen,
+                                         datatype, op, hip_stream);
+    CS_RETURN(reduce_local_indexed_chunked(inbuf, in_displs, inoutbuf, inout_displs, order, runstart, disp_unit,
+                                           nblocks, blocklen, datatype, op, work, work_bytes, hip_stream));
+}
+
+int MPIX_Reduce_local_chunked_worksize(int nblocks, int blocklen, MPI_Datatype datatype, MPI_Aint * work_bytes)
+{
+    static const char *fc = "MPIX_Reduce_local_chunked_worksize";
+    uint64_t bytes = 0;
+    int rc = MPI_SUCCESS, elem = 0;
+    const MPIR_Type_desc *d;
+    MPIR_Dropin_cs_enter(MPIR_DROPIN_CS_GLOBAL);
+    /* (the size needs the datatype's element bytes alone: the described type's class) */
+    if (nblocks < 0 || blocklen < 0) {
+        MPIR_Err_set_detail("negative %s %d", nblocks < 0 ? "nblocks" : "blocklen", nblocks < 0 ? nblocks : blocklen);
+        rc = err_return(fc, MPI_ERR_COUNT);
+    } else if ((d = MPIR_Type_lookup(datatype)) == NULL || (elem = d->elem) == 0) {
+        MPIR_Err_set_detail("datatype 0x%x has no device element class", (unsigned) datatype);
+        rc = err_return(fc, MPI_ERR_TYPE);
+    } else if (work_bytes == NULL) {
+        MPIR_Err_set_detail("work_bytes is NULL");
+        rc = err_return(fc, MPI_ERR_ARG);
+    } else if ((rc = shim_has(MPIR_Hip_chunked_worksize != NULL, "MPIR_Hip_chunked_worksize")) != MPI_SUCCESS) {
+        rc = err_return(fc, rc);
+    } else if (MPIR_Hip_chunked_worksize((uint64_t) nblocks, (uint64_t) blocklen, elem, &bytes) != MPIR_HIP_OK) {
+        MPIR_Err_set_detail("the work of %d blocks of %d elements does not fit an MPI_Aint", nblocks, blocklen);
+        rc = err_return(fc, MPI_ERR_ARG);
+    } else {
+        *work_bytes = (MPI_Aint) bytes;
+    }
+    MPIR_Dropin_cs_exit(MPIR_DROPIN_CS_GLOBAL);
+    return rc;
+}
+
+static int reduce_local_runs(const MPI_Aint * displs, const int *order, int nblocks, int *runstart, void *hip_stream)
+{
+    static const char *fc = "MPIX_Reduce_local_runs";
+    int rc;
+    if (nblocks < 0) {
+        MPIR_Err_set_detail("negative nblocks %d", nblocks);
+        return err_return(fc, MPI_ERR_COUNT);
+    }
+    if (nblocks == 0)
+        return MPI_SUCCESS;
+    if (displs == NULL || order == NULL || runstart == NULL) {
+        MPIR_Err_set_detail("%s is NULL", displs == NULL ? "displs" : order == NULL ? "order" : "runstart");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if ((rc = shim_has(MPIR_Hip_runs_build != NULL, "MPIR_Hip_runs_build")) != MPI_SUCCESS)
+        return err_return(fc, rc);
+    rc = MPIR_Hip_runs_build((const int64_t *) displs, order, (uint64_t) nblocks, runstart, hip_stream,
+                             hip_stream == NULL);
+    return shim_result(fc, rc, "%s needs its three tables in device memory on one device (host tables: the "
+                       "synchronous call only)", "%s: an entry of a host order table is out of range");
+}
+
+int MPIX_Reduce_local_runs(const MPI_Aint * displs, const int *order, int nblocks, int *runstart, void *hip_stream)
+{
+    CS_RETURN(reduce_local_runs(displs, order, nblocks, runstart, hip_stream));
+}
+
 /* ---- MPIX_Reduce_local_ragged: unequal pieces from a table of packed offsets (see the header) */
 #pragma weak MPIR_Hip_reduce_ragged
 static int reduce_local_ragged(const void *inbuf, const MPI_Aint * in_displs, void *inoutbuf,

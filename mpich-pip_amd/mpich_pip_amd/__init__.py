@@ -118,6 +118,9 @@ EXPORTED_SYMBOLS = [
     "MPIX_Reduce_local_indexed", "MPIR_Hip_reduce_indexed", "MPIR_Hip_indexed_plan_info",
     "MPIX_Reduce_local_indexed_ordered", "MPIR_Hip_reduce_indexed_ordered", "MPIR_Hip_indexed_ordered_plan_info",
     "MPIX_Reduce_local_order", "MPIX_Reduce_local_order_worksize", "MPIR_Hip_order_build", "MPIR_Hip_order_worksize",
+    "MPIX_Reduce_local_indexed_chunked", "MPIX_Reduce_local_chunked_worksize", "MPIX_Reduce_local_runs",
+    "MPIR_Hip_reduce_indexed_chunked", "MPIR_Hip_indexed_chunked_plan_info", "MPIR_Hip_chunked_worksize",
+    "MPIR_Hip_runs_build",
     "MPIX_Reduce_local_ragged", "MPIR_Hip_reduce_ragged", "MPIR_Hip_ragged_plan_info",
     "MPIX_Reduce_local_fetch_ragged", "MPIR_Hip_reduce_fetch_ragged", "MPIR_Hip_fetch_ragged_plan_info",
     "MPIX_Reduce_local_fetch_indexed_ordered", "MPIR_Hip_reduce_fetch_indexed_ordered",
@@ -228,6 +231,22 @@ def load(path: str | None = None) -> ctypes.CDLL:
     lib.MPIR_Hip_order_build.restype = i32
     lib.MPIR_Hip_order_worksize.argtypes = [u64, ctypes.POINTER(u64)]
     lib.MPIR_Hip_order_worksize.restype = i32
+    lib.MPIX_Reduce_local_indexed_chunked.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_long, i32, i32, i32, i32, vp,
+                                                      ctypes.c_long, vp]
+    lib.MPIX_Reduce_local_indexed_chunked.restype = i32
+    lib.MPIX_Reduce_local_chunked_worksize.argtypes = [i32, i32, i32, ctypes.POINTER(ctypes.c_long)]
+    lib.MPIX_Reduce_local_chunked_worksize.restype = i32
+    lib.MPIX_Reduce_local_runs.argtypes = [vp, vp, i32, vp, vp]
+    lib.MPIX_Reduce_local_runs.restype = i32
+    lib.MPIR_Hip_reduce_indexed_chunked.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, vp, u64, vp, i32]
+    lib.MPIR_Hip_reduce_indexed_chunked.restype = i32
+    lib.MPIR_Hip_indexed_chunked_plan_info.argtypes = [vp, vp, vp, vp, vp, vp, u64, u64, u64, i32, i32,
+                                                       ctypes.POINTER(u64)]
+    lib.MPIR_Hip_indexed_chunked_plan_info.restype = i32
+    lib.MPIR_Hip_chunked_worksize.argtypes = [u64, u64, i32, ctypes.POINTER(u64)]
+    lib.MPIR_Hip_chunked_worksize.restype = i32
+    lib.MPIR_Hip_runs_build.argtypes = [vp, vp, u64, vp, vp, i32]
+    lib.MPIR_Hip_runs_build.restype = i32
     lib.MPIX_Reduce_local_ragged.argtypes = [vp, vp, vp, vp, vp, ctypes.c_long, i32, i32, i32, i32, vp]
     lib.MPIX_Reduce_local_ragged.restype = i32
     lib.MPIR_Hip_reduce_ragged.argtypes = [vp, vp, vp, vp, vp, u64, u64, u64, i32, i32, vp, i32]
@@ -679,6 +698,67 @@ def indexed_ordered_plan_info(inbuf: int, in_displs, inoutbuf: int, inout_displs
     if rc:
         raise LookupError(f"MPIR_Hip_indexed_ordered_plan_info: {rc}")
     return dict(zip(("form", "launches", "groups", "per", "threshold", "rows_per_launch"), (int(v) for v in out)))
+
+
+# ---- chunked indexed reductions (MPIX_Reduce_local_indexed_chunked)
+REDUCE_LOCAL_CHUNK = 64
+
+
+def reduce_local_indexed_chunked(inbuf: int, in_displs, inoutbuf: int, inout_displs, order, runstart, disp_unit: int,
+                                 nblocks: int, blocklen: int, datatype: int, op: int, work: int = 0, work_bytes: int = 0,
+                                 stream: int = 0) -> int:
+    """MPIX_Reduce_local_indexed_chunked: reduce_local_indexed_ordered's operands,
+    the blocks of one target folded in chunks of REDUCE_LOCAL_CHUNK counted from
+    the run's first block, then the partials into the target.  order and runstart:
+    int32 tables (raw addresses or numpy arrays, see _order_addr; reduce_local_order
+    and reduce_local_runs make them); both None: the indexed call.  work: a raw
+    device address of work_bytes bytes (reduce_local_chunked_worksize), or 0 (the
+    library's own buffer: the synchronous call only)."""
+    return load().MPIX_Reduce_local_indexed_chunked(
+        ctypes.c_void_p(inbuf or None), ctypes.c_void_p(_table_addr(in_displs) or None), ctypes.c_void_p(inoutbuf or None),
+        ctypes.c_void_p(_table_addr(inout_displs) or None), ctypes.c_void_p(_order_addr(order) or None),
+        ctypes.c_void_p(_order_addr(runstart) or None), disp_unit, nblocks, blocklen, datatype, op,
+        ctypes.c_void_p(work or None), work_bytes, ctypes.c_void_p(stream or None))
+
+
+def reduce_local_chunked_worksize(nblocks: int, blocklen: int, datatype: int) -> int:
+    """MPIX_Reduce_local_chunked_worksize: the bytes of scratch
+    reduce_local_indexed_chunked may use (no GPU needed).  Raises ValueError where
+    it refuses."""
+    out = ctypes.c_long(0)
+    rc = load().MPIX_Reduce_local_chunked_worksize(nblocks, blocklen, datatype, ctypes.byref(out))
+    if rc:
+        raise ValueError(f"MPIX_Reduce_local_chunked_worksize: {error_string(rc)}")
+    return int(out.value)
+
+
+def reduce_local_runs(displs, order, nblocks: int, runstart, stream: int = 0) -> int:
+    """MPIX_Reduce_local_runs: runstart[p] = the first sorted position of the run
+    position p lies in.  displs: a raw address or a numpy int64 array; order and
+    runstart (written): raw addresses or numpy int32 arrays."""
+    return load().MPIX_Reduce_local_runs(ctypes.c_void_p(_table_addr(displs) or None),
+                                         ctypes.c_void_p(_order_addr(order) or None), nblocks,
+                                         ctypes.c_void_p(_order_addr(runstart) or None), ctypes.c_void_p(stream or None))
+
+
+def indexed_chunked_plan_info(inbuf: int, in_displs, inoutbuf: int, inout_displs, order, runstart, disp_unit: int,
+                              nblocks: int, blocklen: int, datatype: int, op: int) -> dict:
+    """MPIR_Hip_indexed_chunked_plan_info: indexed_ordered_plan_info's outputs for
+    ONE of the chunked call's two kernels (they share form, launches and groups),
+    then total_launches (both kernels) and work_bytes.  Raises as
+    indexed_plan_info does."""
+    out = (ctypes.c_uint64 * 8)()
+    rc = load().MPIR_Hip_indexed_chunked_plan_info(
+        ctypes.c_void_p(inbuf or None), ctypes.c_void_p(_table_addr(in_displs) or None), ctypes.c_void_p(inoutbuf or None),
+        ctypes.c_void_p(_table_addr(inout_displs) or None), ctypes.c_void_p(_order_addr(order) or None),
+        ctypes.c_void_p(_order_addr(runstart) or None), disp_unit, nblocks, blocklen, op & 0xFF,
+        _ELEM_BY_HANDLE[datatype], out)
+    if rc == MPIR_HIP_EARG:
+        raise ValueError("MPIR_Hip_indexed_chunked_plan_info: arguments refused")
+    if rc:
+        raise LookupError(f"MPIR_Hip_indexed_chunked_plan_info: {rc}")
+    return dict(zip(("form", "launches", "groups", "per", "threshold", "rows_per_launch", "total_launches", "work_bytes"),
+                    (int(v) for v in out)))
 
 
 # ---- ragged reductions (MPIX_Reduce_local_ragged)
