@@ -308,6 +308,70 @@ MPICH_API_PUBLIC int MPIX_Reduce_local_batch(const MPIX_Reduce_local_seg *segs, 
 MPICH_API_PUBLIC int MPIX_Reduce_local_strided(const void *inbuf, MPI_Aint in_stride,
                               void *inoutbuf, MPI_Aint inout_stride, int nblocks, int blocklen,
                               MPI_Datatype datatype, MPI_Op op, void *hip_stream);
+/* Subarray local reduction: a sub-box of an N-dimensional array on either side,
+ * with no table -- ghost cells folded back onto the owner's interior, a packed
+ * halo buffer accumulated into an interior region, a periodic boundary wrapped
+ * inside one array.  Each operand is what
+ *   MPI_Type_create_subarray(ndims, X_sizes, subsizes, X_starts, order, datatype, &t)
+ * describes, applied once to X buf, the origin of the whole array; layout and
+ * the meaning of `order` (MPI_ORDER_C: the last dimension the fastest,
+ * MPI_ORDER_FORTRAN: the first) are the reference's
+ * (src/mpi/datatype/type_create_subarray.c:185-258).  X_sizes NULL: that operand
+ * is packed -- its sizes are subsizes, its starts 0, X_starts is not looked at.
+ * For every index tuple of the box the element of inoutbuf becomes what
+ * MPI_Reduce_local on that one pair of elements leaves, bit for bit; every
+ * contiguous row of the box is bit-identical to MPI_Reduce_local on it; no byte
+ * of either array outside its box is read or written.
+ *   hip_stream NULL: synchronous on the calling thread's library stream;
+ *       otherwise enqueued on that stream without waiting.  Everything travels
+ *       in the kernel arguments: no argument array is read after the call
+ *       returns, and a call on a stream is captured into a graph as a linear
+ *       chain with nothing to keep alive.
+ *   Checked in this order, all before the first launch, so that a call that
+ *   returns an error has modified nothing:
+ *   1. Builtin ops and basic types as the strided call validates them
+ *       (MPI_REPLACE, MPI_NO_OP, null, invalid and user ops: MPI_ERR_OP;
+ *       MPI_LAND / MPI_LOR on floating types: MPI_ERR_OP).
+ *   2. ndims < 1 or > MPIX_REDUCE_LOCAL_SUBARRAY_MAXDIMS: MPI_ERR_DIMS.  subsizes
+ *       NULL, or X_sizes given with X_starts NULL: MPI_ERR_ARG.  order neither
+ *       constant: MPI_ERR_ARG.
+ *   3. Per dimension in ascending order, inbuf's side then inoutbuf's, as
+ *       type_create_subarray.c:104-133 checks them: size < 1, subsize < 1,
+ *       start < 0, subsize > size, start > size - subsize: each MPI_ERR_ARG.  An
+ *       empty box is refused, as the reference refuses it.
+ *   4. The product of an operand's sizes times the datatype's size not fitting
+ *       an MPI_Aint: MPI_ERR_ARG.
+ *   5. MPI_IN_PLACE for either buffer: MPI_ERR_BUFFER.
+ *   6. inbuf == inoutbuf under MPIR_CVAR_COLL_ALIAS_CHECK: MPI_ERR_BUFFER, unless
+ *       both sides give sizes, the two size arrays are equal and the boxes are
+ *       disjoint: some dimension has |in_starts[d] - inout_starts[d]| >=
+ *       subsizes[d].  That is the periodic wrap inside one array.  Any other
+ *       overlap of the input box with the output box is undefined and not checked.
+ *   7. The first and the last byte of each operand's box must be device memory
+ *       on one device (MPI_ERR_BUFFER).  Host operands are not taken.
+ * The box is brought to a row of contiguous elements under k outer dimensions
+ * (dimensions of subsize 1 dropped; a dimension the box spans on both sides
+ * merged into the next).  k == 0 is the single call and k == 1
+ * MPIX_Reduce_local_strided, each with everything it does; k == 2 or 3 is one
+ * launch of a kernel of its own (more only past 2^23 workgroups); from k == 4 on
+ * the outermost k - 3 dimensions are looped on the host as back-to-back launches
+ * on the same stream.  The wide / narrow threshold is the strided call's.
+ * Measured (tools/subarray_ab.py; DESIGN.md, Subarray reductions): the 254^3
+ * interior of a 256^3 array of doubles in 102 us against 4.6 ms for the loop of
+ * 254 strided calls and 105 us for MPIX_Reduce_local_indexed over a device table
+ * of the 64,516 rows; its one-cell face across the fast axis in 18.8 us against
+ * 2.6 ms and 22.7 us.  One call costs what 1.1 to 5.9 planes of the loop cost; it
+ * was ahead of the indexed call at every shape tried, by 1.4-3.7 % on 2 KiB rows
+ * and 12-21 % on rows of one or two elements.  A box that collapses to one outer
+ * dimension runs 0.3-0.5 us above the strided call it becomes. */
+#define MPI_ERR_DIMS      11     /* mpi.h.in:802 */
+#define MPI_ORDER_C       56     /* mpi.h.in:537-538 */
+#define MPI_ORDER_FORTRAN 57
+#define MPIX_REDUCE_LOCAL_SUBARRAY_MAXDIMS 8
+MPICH_API_PUBLIC int MPIX_Reduce_local_subarray(const void *inbuf, const int in_sizes[], const int in_starts[],
+                              void *inoutbuf, const int inout_sizes[], const int inout_starts[],
+                              int ndims, const int subsizes[], int order,
+                              MPI_Datatype datatype, MPI_Op op, void *hip_stream);
 /* Fetching local reduction: the old value out and the combine in one pass -- the
  * target side of MPI_Get_accumulate / MPI_Fetch_and_op, which copies the target's
  * old contents into the response buffer and then combines the origin's data into

@@ -192,6 +192,56 @@ uint64_t MPIR_Hip_set_strided_wide_bytes(uint64_t bytes);
  * Returns the previous value. */
 uint64_t MPIR_Hip_strided_test_max_groups(uint64_t groups);
 
+/* Subarray reduction: every row of a sub-box of an N-dimensional array combined
+ * as MPIR_Hip_reduce combines it, no table and, for boxes of up to three outer
+ * dimensions, one launch.  Each operand is what MPI_Type_create_subarray(ndims,
+ * X_sizes, subsizes, X_starts, order, ...) describes at X buf, the origin of the
+ * whole array (c_order != 0: MPI_ORDER_C, the last dimension the fastest; else
+ * MPI_ORDER_FORTRAN); X_sizes NULL: that operand is packed (sizes = subsizes,
+ * starts 0, X_starts not looked at).  The planner brings the box to a normal
+ * form -- the fastest dimension first; a dimension of subsize 1 dropped;
+ * dimension d + 1 merged into d where the box spans all of d on both sides (an
+ * outer dimension's merged count stays below 2^31) -- a row of blocklen
+ * contiguous elements under k outer dimensions, each a count and one byte stride
+ * per side.  k == 0 is MPIR_Hip_reduce, k == 1 MPIR_Hip_reduce_strided, both
+ * with everything they do; k == 2 or 3 is k_reduce_subarray, in the strided
+ * call's three forms at the strided call's threshold and per-launch cap
+ * (MPIR_Hip_set_strided_wide_bytes, MPIR_Hip_strided_test_max_groups); the
+ * dimensions past the third are looped on the host, back-to-back launches on the
+ * same stream.  The first and the last byte of each box must be device memory
+ * on one device (MPIR_HIP_EBUFFER), settled before the first launch.  ndims
+ * outside 1..MPIR_HIP_SUBARRAY_MAXDIMS, subsizes NULL, sizes without starts, a
+ * dimension the reference refuses (size < 1, subsize < 1, start < 0, subsize >
+ * size, start > size - subsize) or an array whose bytes pass 63 bits:
+ * MPIR_HIP_EARG.  MPIR_HIP_ENOKERNEL for REPLACE and pairs with no kernel.
+ * Nothing of the caller's arrays is read after the call returns. */
+#define MPIR_HIP_SUBARRAY_MAXDIMS 8
+int MPIR_Hip_reduce_subarray(const void *inbuf, const int *in_sizes, const int *in_starts, void *inoutbuf,
+                             const int *io_sizes, const int *io_starts, int ndims, const int *subsizes, int c_order,
+                             int op, int elem, void *hip_stream, int sync);
+
+/* For tests and tools: the normal form and the launches of MPIR_Hip_reduce_subarray
+ * for device operands at these addresses (host arithmetic on the arguments only).
+ * out[0] form; out[1] launches; out[2] workgroups over all launches; out[3] G
+ * (WIDE) or units per workgroup (NARROW); out[4] units per row (NARROW); out[5]
+ * the wide / narrow threshold in force; out[6] rows per launch; out[7] k; out[8]
+ * blocklen; out[9] / out[10] the byte offsets of the input and output box in
+ * their arrays; STRIDED only: out[11] the strided call's form, out[12] / out[13]
+ * its rows on the tile and the element path, and out[1..3], out[5], out[6] as
+ * MPIR_Hip_strided_plan_info reports them; out[16 + d], out[24 + d], out[32 + d]
+ * for d < k: outer dimension d's count and its byte stride in the input and the
+ * output.  SINGLE reports MPIR_Hip_plan_info's grid as its workgroups.  Returns
+ * as MPIR_Hip_reduce_subarray does for the same arguments, residency apart. */
+#define MPIR_HIP_SUBARRAY_SINGLE       1   /* k == 0: MPIR_Hip_reduce's own plan */
+#define MPIR_HIP_SUBARRAY_WIDE         2   /* the forms of k >= 2: MPIR_HIP_STRIDED_WIDE, ... */
+#define MPIR_HIP_SUBARRAY_NARROW_VEC   3
+#define MPIR_HIP_SUBARRAY_NARROW_ELEMS 4
+#define MPIR_HIP_SUBARRAY_STRIDED      5   /* k == 1: MPIR_Hip_reduce_strided's own plan */
+#define MPIR_HIP_SUBARRAY_PLAN_WORDS  40
+int MPIR_Hip_subarray_plan_info(const void *inbuf, const int *in_sizes, const int *in_starts, const void *inoutbuf,
+                                const int *io_sizes, const int *io_starts, int ndims, const int *subsizes, int c_order,
+                                int op, int elem, uint64_t out[MPIR_HIP_SUBARRAY_PLAN_WORDS]);
+
 /* Fetching reduction: for i < count, fetchbuf[i] = the bytes inoutbuf[i] held on
  * entry and inoutbuf[i] = op(inoutbuf[i], inbuf[i]), in one kernel launch that
  * reads inoutbuf once -- the target side of MPI_Get_accumulate / MPI_Fetch_and_op

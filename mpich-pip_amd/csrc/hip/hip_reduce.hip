@@ -35,6 +35,7 @@ Entry g_table[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 multi_fn g_multi[MPIR_HIP_NOPS][MPIR_HIP_NELEMS][2][kMultiMaxP - 1];
 BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+SubarrayEntry g_subarray[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 OrderedEntry g_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 ChunkedEntry g_chunked[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];

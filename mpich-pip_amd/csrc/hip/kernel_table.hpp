@@ -40,6 +40,7 @@ typedef void (*split_fn)(const void *const *, int, const void *, uint64_t, Combi
 typedef hipError_t (*batch_fn)(const BatchArgs *, uint64_t, hipStream_t);
 typedef uint64_t (*bgroups_fn)(const void *, const void *, uint64_t, int *);
 typedef hipError_t (*strided_fn)(const StridedArgs *, uint64_t, hipStream_t);
+typedef hipError_t (*subarray_fn)(const SubarrayArgs *, uint64_t, hipStream_t);
 typedef hipError_t (*fetch_fn)(const FetchArgs *, hipStream_t);
 typedef hipError_t (*indexed_fn)(const IndexedArgs *, uint64_t, hipStream_t);
 typedef hipError_t (*ordered_fn)(const OrderedArgs *, uint64_t, hipStream_t);
@@ -71,6 +72,10 @@ struct BatchEntry { batch_fn launch; bgroups_fn groups; };
 // the pairs g_batch holds (reg_strided<>, from the reg_strided_*.hip units); a
 // row's path and workgroups are g_batch's `groups`.
 struct StridedEntry { strided_fn launch; };
+// g_subarray[op][elem], likewise: launch_subarray<Op, T>, one launch of
+// k_reduce_subarray over a range of rows of a sub-box (MPIR_Hip_reduce_subarray),
+// for the pairs g_strided holds (reg_subarray<>, from the reg_subarray_*.hip units).
+struct SubarrayEntry { subarray_fn launch; };
 // g_fetch[op][elem], likewise: launch_fetch<Op, T>, the one launch of
 // k_reduce_fetch (MPIR_Hip_reduce_fetch), for the pairs g_batch holds
 // (reg_fetch<>, from the reg_fetch_*.hip units); plan = fetch_plan<T>, the plan
@@ -187,6 +192,7 @@ void host_loop(const void *in, void *io, uint64_t n) {
 extern Entry g_table[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern BatchEntry g_batch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern StridedEntry g_strided[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
+extern SubarrayEntry g_subarray[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern FetchEntry g_fetch[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern IndexedEntry g_indexed[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
 extern OrderedEntry g_ordered[MPIR_HIP_NOPS][MPIR_HIP_NELEMS];
@@ -225,6 +231,11 @@ void reg_wide(int op, int elem) {
 template <class Op, class T>
 void reg_strided(int op, int elem) {
     g_strided[op][elem] = StridedEntry{&launch_strided<Op, T>};
+}
+// the subarray kernel of the same pairs, from the reg_subarray_*.hip units
+template <class Op, class T>
+void reg_subarray(int op, int elem) {
+    g_subarray[op][elem] = SubarrayEntry{&launch_subarray<Op, T>};
 }
 // the fetching kernel of the same pairs, from the reg_fetch_*.hip units
 template <class Op, class T>

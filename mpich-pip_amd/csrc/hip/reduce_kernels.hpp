@@ -922,6 +922,148 @@ hipError_t launch_strided(const StridedArgs *a, uint64_t groups, hipStream_t s) 
 }
 
 // ============================================================================
+// Subarray reductions (MPIR_Hip_reduce_subarray): the rows of a sub-box of an
+// N-dimensional array, each row's result what the single call gives on it.  The
+// host brings the box to a row of blocklen contiguous elements under up to three
+// outer dimensions (more are looped on the host), each with a count and one byte
+// stride per side.  It is the strided kernel with the row's address a sum over
+// the outer indices where that kernel has one product: rows are numbered with
+// outer dimension 1 fastest, row r = i1 + n1 * (i2 + n2 * i3) at
+// i1 * stride[0] + i2 * stride[1] + i3 * stride[2] of either side.  112 bytes of
+// kernel arguments, no table.  The forms are the strided kernel's:
+//
+//   * WIDE: the grid is nrows x G; workgroup wg takes row wg / G of the launch,
+//     finds its outer indices on uniform values (subarray_step: two 32-bit
+//     divisions), forms both row pointers from blockIdx and the arguments alone
+//     (the tile's buffer descriptors stay in scalar registers) and runs
+//     reduce_seg with tile wg % G.
+//   * NARROW: the rows flattened into units as the strided kernel flattens them.
+//     The workgroup divides its first unit by the units per row once and finds
+//     that row's outer indices, all uniform; a lane's row is at most 16383
+//     further on: the strided kernel's one 32-bit division gives its distance,
+//     subarray_step from the workgroup's indices its own.
+//
+// A launch names its first row by that row's outer indices (first[]): later
+// launches of a call continue at a later row with the same two pointers, since
+// the rows of one launch do not share one stride.  No LDS, no scratch, no gridDim.
+// ============================================================================
+struct SubarrayArgs {
+    const char *in;         // the input box's first element
+    char *io;
+    uint64_t blocklen;      // elements per row, > 0
+    uint64_t in_stride[3];  // bytes per step of outer dimension 1, 2, 3 (a dimension not in use: 0)
+    uint64_t io_stride[3];
+    uint32_t n[3];          // the outer dimensions' counts, 1 to 2^31 - 1 (not in use: 1)
+    uint32_t first[3];      // outer indices of this launch's row 0, first[d] < n[d]
+    uint32_t nrows;         // rows of this launch, > 0
+    uint32_t form;          // MPIR_HIP_STRIDED_WIDE / _NARROW_VEC / _NARROW_ELEMS
+    uint32_t per;           // WIDE: G, workgroups per row; NARROW: units per row
+    uint32_t pad_;
+};
+static_assert(sizeof(SubarrayArgs) == 112, "the subarray kernel's arguments");
+
+// The outer indices i[] of the row q rows after the row at f[] (f[d] < n[d]), in
+// 32 bits: a remainder and a start are both below 2^31, and so is each carry's sum.
+// The row is one of the box (the caller bounds q by the launch's rows), so i[2]
+// needs no reduction.
+__device__ __forceinline__ void subarray_step(const SubarrayArgs &a, const uint32_t f[3], uint32_t q, uint32_t i[3]) {
+    const uint32_t q1 = q / a.n[0];
+    uint32_t i1 = f[0] + (q - q1 * a.n[0]);
+    uint32_t carry = i1 >= a.n[0];
+    i1 -= carry ? a.n[0] : 0;
+    const uint32_t q2 = q1 / a.n[1];
+    uint32_t i2 = f[1] + (q1 - q2 * a.n[1]) + carry;
+    carry = i2 >= a.n[1];
+    i2 -= carry ? a.n[1] : 0;
+    i[0] = i1;
+    i[1] = i2;
+    i[2] = f[2] + q2 + carry;
+}
+
+__device__ __forceinline__ uint64_t subarray_off(const uint64_t stride[3], const uint32_t i[3]) {
+    return i[0] * stride[0] + i[1] * stride[1] + i[2] * stride[2];
+}
+
+template <class Op, class T>
+__device__ __forceinline__ void reduce_subarray_narrow(const SubarrayArgs &a) {
+    const uint32_t upr = a.per;                             // units per row
+    const unsigned t = threadIdx.x;
+    uint32_t b[3], i[3];                                    // the workgroup's first row, a lane's row
+    if constexpr (sizeof(T) <= 16) {
+        if (a.form == MPIR_HIP_STRIDED_NARROW_VEC) {
+            constexpr uint32_t upw = strided_units_per_group<T>(true);
+            constexpr int per_lane = (int)(upw / kThreads);
+            const uint64_t u0 = (uint64_t)blockIdx.x * upw;
+            const uint64_t row0 = u0 / upr;
+            const uint32_t col0 = (uint32_t)(u0 - row0 * upr);
+            subarray_step(a, a.first, (uint32_t)row0, b);
+            u32x4 x[per_lane], y[per_lane];
+            u32x4 *po[per_lane];
+            bool ok[per_lane];
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j) {
+                const uint32_t c = col0 + t + (uint32_t)j * kThreads;
+                const uint32_t q = c / upr;
+                const uint64_t off = (uint64_t)(c - q * upr) * 16;
+                ok[j] = row0 + q < a.nrows;
+                if (ok[j]) {
+                    subarray_step(a, b, q, i);
+                    po[j] = reinterpret_cast<u32x4 *>(a.io + subarray_off(a.io_stride, i) + off);
+                    x[j] = __builtin_nontemporal_load(po[j]);
+                    y[j] = __builtin_nontemporal_load(
+                        reinterpret_cast<const u32x4 *>(a.in + subarray_off(a.in_stride, i) + off));
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < per_lane; ++j)
+                if (ok[j]) __builtin_nontemporal_store(combine16<Op, T>(x[j], y[j]), po[j]);
+            return;
+        }
+    }
+    constexpr uint32_t upw = strided_units_per_group<T>(false);
+    const uint64_t u0 = (uint64_t)blockIdx.x * upw;
+    const uint64_t row0 = u0 / upr;
+    const uint32_t col0 = (uint32_t)(u0 - row0 * upr);
+    subarray_step(a, a.first, (uint32_t)row0, b);
+    for (uint32_t k = t; k < upw; k += kThreads) {
+        const uint32_t c = col0 + k;
+        const uint32_t q = c / upr;
+        if (row0 + q >= a.nrows) break;                     // rows only grow with k
+        subarray_step(a, b, q, i);
+        batch_elem_at<Op, T>(a.in + subarray_off(a.in_stride, i), a.io + subarray_off(a.io_stride, i), c - q * upr);
+    }
+}
+
+template <class Op, class T>
+__global__ __launch_bounds__(kThreads) void k_reduce_subarray(SubarrayArgs a) {
+    if (a.form == MPIR_HIP_STRIDED_WIDE) {
+        const uint32_t row = blockIdx.x / a.per;
+        if (row >= a.nrows) return;
+        uint32_t i[3];
+        subarray_step(a, a.first, row, i);
+        reduce_seg<Op, T>(a.in + subarray_off(a.in_stride, i), a.io + subarray_off(a.io_stride, i), a.blocklen,
+                          blockIdx.x - row * a.per);
+        return;
+    }
+    reduce_subarray_narrow<Op, T>(a);
+}
+
+// one launch: `groups` workgroups over a.nrows rows from the row at a.first (the
+// planner's count, as for launch_strided)
+template <class Op, class T>
+hipError_t launch_subarray(const SubarrayArgs *a, uint64_t groups, hipStream_t s) {
+    if (!a->nrows || !a->per || !a->blocklen || !a->n[0] || !a->n[1] || !a->n[2] || a->first[0] >= a->n[0] ||
+        a->first[1] >= a->n[1] || a->first[2] >= a->n[2] || groups < 1 || groups > kBatchMaxGroups)
+        return hipErrorInvalidValue;
+    // the launch's last row is a row of the box: no index leaves its dimension
+    const unsigned __int128 n01 = (unsigned __int128)a->n[0] * a->n[1];
+    if (a->first[0] + (unsigned __int128)a->n[0] * a->first[1] + n01 * a->first[2] + a->nrows > n01 * a->n[2])
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_reduce_subarray<Op, T>), dim3((unsigned)groups), dim3(kThreads), 0, s, *a);
+    return hipGetLastError();
+}
+
+// ============================================================================
 // Indexed reductions (MPIR_Hip_reduce_indexed): nrows equal blocks of blocklen
 // elements, block k at in + in_displs[k] * disp_unit and io + io_displs[k] *
 // disp_unit (signed displacements, device tables), a side with no table packed

@@ -1,5 +1,5 @@
 // table_calls.hip -- the shim's calls on many blocks at once: MPIR_Hip_reduce_batch,
-// _strided, _fetch, _indexed, _indexed_ordered, _indexed_chunked, _ragged,
+// _strided, _subarray, _fetch, _indexed, _indexed_ordered, _indexed_chunked, _ragged,
 // _fetch_ragged, _fetch_indexed_ordered, MPIR_Hip_cas_indexed_ordered,
 // MPIR_Hip_order_build and MPIR_Hip_runs_build, with their *_plan_info functions.  Every one settles residency before it
 // enqueues (a call that fails has written nothing) and then runs on one call
@@ -350,6 +350,160 @@ void strided_launches(const StridedPlan &p, const void *in, uint64_t in_stride, 
                             (uint32_t)(p.form == MPIR_HIP_STRIDED_WIDE ? p.per : p.upr), 0};
         if (!emit(a, strided_launch_groups(p, n))) return;
     }
+}
+
+// ---- subarray calls: a sub-box of an N-dimensional array on either side.
+// The normal form of a call's two boxes: a row of blocklen contiguous elements
+// under k outer dimensions, dimension 0 the fastest, each with a count and one
+// byte stride per side; where each box begins and ends in its array.  A pure
+// function of the integer arguments.
+static_assert(MPIR_HIP_SUBARRAY_SINGLE == MPIR_HIP_STRIDED_SINGLE && MPIR_HIP_SUBARRAY_WIDE == MPIR_HIP_STRIDED_WIDE &&
+                  MPIR_HIP_SUBARRAY_NARROW_VEC == MPIR_HIP_STRIDED_NARROW_VEC &&
+                  MPIR_HIP_SUBARRAY_NARROW_ELEMS == MPIR_HIP_STRIDED_NARROW_ELEMS,
+              "the subarray kernel's forms are the strided forms");
+struct SubarrayBox {
+    int k;
+    uint64_t blocklen;
+    uint64_t n[MPIR_HIP_SUBARRAY_MAXDIMS];
+    uint64_t in_stride[MPIR_HIP_SUBARRAY_MAXDIMS], io_stride[MPIR_HIP_SUBARRAY_MAXDIMS];     // bytes
+    uint64_t in_off, io_off;        // bytes from the array's origin to the box's first element
+    uint64_t in_span, io_span;      // bytes from the box's first to one past its last
+};
+
+// one side's sizes and starts, fastest dimension first (null sizes: packed) -- the
+// reference's per-dimension checks (type_create_subarray.c:104-133), the element
+// strides and the array's bytes.  False: a check fails, or the bytes pass 63 bits.
+bool subarray_side(const int *sizes, const int *starts, const int *subsizes, int ndims, int c_order, uint64_t esz,
+                   uint64_t stride[], uint64_t *off) {
+    uint64_t elems = 1;
+    *off = 0;
+    for (int j = 0; j < ndims; ++j) {
+        const int d = c_order ? ndims - 1 - j : j;
+        const int64_t size = sizes ? sizes[d] : subsizes[d], start = sizes ? starts[d] : 0, sub = subsizes[d];
+        if (size < 1 || sub < 1 || start < 0 || sub > size || start > size - sub) return false;
+        stride[j] = elems;
+        *off += (uint64_t)start * elems * esz;
+        if (__builtin_mul_overflow(elems, (uint64_t)size, &elems) || elems > (~(uint64_t)0 >> 1) / esz) return false;
+    }
+    return true;
+}
+
+// MPIR_HIP_EARG where the arguments are not a box the reference would build
+int subarray_box(const int *in_sizes, const int *in_starts, const int *io_sizes, const int *io_starts, int ndims,
+                 const int *subsizes, int c_order, uint64_t esz, SubarrayBox &b) {
+    if (ndims < 1 || ndims > MPIR_HIP_SUBARRAY_MAXDIMS || !subsizes || (in_sizes && !in_starts) ||
+        (io_sizes && !io_starts))
+        return MPIR_HIP_EARG;
+    uint64_t is[MPIR_HIP_SUBARRAY_MAXDIMS], os[MPIR_HIP_SUBARRAY_MAXDIMS];
+    if (!subarray_side(in_sizes, in_starts, subsizes, ndims, c_order, esz, is, &b.in_off) ||
+        !subarray_side(io_sizes, io_starts, subsizes, ndims, c_order, esz, os, &b.io_off))
+        return MPIR_HIP_EARG;
+    // a dimension of subsize 1 only moved the base; dimension d + 1 joins d where
+    // the box spans all of d on both sides.  An outer dimension's count stays
+    // below 2^31 (the kernel's indices are 32-bit): past that it is left unmerged.
+    uint64_t n[MPIR_HIP_SUBARRAY_MAXDIMS];
+    int m = 0;
+    for (int j = 0; j < ndims; ++j) {
+        const uint64_t sub = (uint64_t)subsizes[c_order ? ndims - 1 - j : j];
+        if (sub == 1) continue;
+        if (m && is[j] == n[m - 1] * is[m - 1] && os[j] == n[m - 1] * os[m - 1] &&
+            ((is[m - 1] == 1 && os[m - 1] == 1 && m == 1) || n[m - 1] * sub < ((uint64_t)1 << 31))) {
+            n[m - 1] *= sub;
+            continue;
+        }
+        n[m] = sub;
+        is[m] = is[j];
+        os[m] = os[j];
+        ++m;
+    }
+    const int row = m && is[0] == 1 && os[0] == 1;
+    b.blocklen = row ? n[0] : 1;
+    b.k = m - row;
+    b.in_span = b.io_span = b.blocklen * esz;
+    for (int d = 0; d < b.k; ++d) {
+        b.n[d] = n[d + row];
+        b.in_stride[d] = is[d + row] * esz;
+        b.io_stride[d] = os[d + row] * esz;
+        b.in_span += (b.n[d] - 1) * b.in_stride[d];
+        b.io_span += (b.n[d] - 1) * b.io_stride[d];
+    }
+    return MPIR_HIP_OK;
+}
+
+// the dimensions one launch covers, and its rows
+int subarray_inner(const SubarrayBox &b) { return std::min(b.k, 3); }
+uint64_t subarray_rows(const SubarrayBox &b) {
+    uint64_t rows = 1;
+    for (int d = 0; d < subarray_inner(b); ++d) rows *= b.n[d];
+    return rows;
+}
+
+// The plan of a box of two or three outer dimensions, or of each of the
+// `*peel` such boxes a call of more is looped over: the strided call's plan of
+// their rows, with every outer stride where that call has one -- the peeled
+// dimensions' too, so that one plan serves every box of the loop.
+void subarray_plan(const SubarrayBox &b, const void *in, const void *io, int elem, StridedPlan &p, uint64_t *peel) {
+    uint64_t in_or = 0, io_or = 0;
+    *peel = 1;
+    for (int d = 0; d < b.k; ++d) {
+        in_or |= b.in_stride[d];
+        io_or |= b.io_stride[d];
+        if (d >= subarray_inner(b)) *peel *= b.n[d];
+    }
+    row_plan(subarray_rows(b), b.blocklen, elem,
+             in_or | io_or | reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(io),
+             [&](uint64_t row_bytes, uint64_t esz) { return strided_row_groups_max(row_bytes, esz, io, io_or); }, p);
+}
+
+// The launches of a plan (in, io: the boxes' first elements): per box of the
+// peeled dimensions, later row ranges named by their first row's outer indices.
+// emit(args, groups) per launch, until it returns false.
+template <class F>
+void subarray_launches(const SubarrayBox &b, const StridedPlan &p, const char *in, char *io, F emit) {
+    const int ki = subarray_inner(b);
+    const uint64_t rows = subarray_rows(b);
+    uint64_t at[MPIR_HIP_SUBARRAY_MAXDIMS] = {0};           // the peeled dimensions' indices
+    for (;;) {
+        SubarrayArgs a;
+        memset(&a, 0, sizeof a);
+        a.in = in;
+        a.io = io;
+        for (int d = ki; d < b.k; ++d) {
+            a.in += at[d] * b.in_stride[d];
+            a.io += at[d] * b.io_stride[d];
+        }
+        a.blocklen = b.blocklen;
+        for (int d = 0; d < 3; ++d) {
+            a.n[d] = d < ki ? (uint32_t)b.n[d] : 1;
+            a.in_stride[d] = d < ki ? b.in_stride[d] : 0;
+            a.io_stride[d] = d < ki ? b.io_stride[d] : 0;
+        }
+        a.form = (uint32_t)p.form;
+        a.per = (uint32_t)(p.form == MPIR_HIP_STRIDED_WIDE ? p.per : p.upr);
+        for (uint64_t row0 = 0; row0 < rows; row0 += p.rows_per_launch) {
+            const uint64_t n = std::min(p.rows_per_launch, rows - row0);
+            uint64_t r = row0;
+            for (int d = 0; d < 3; ++d) {
+                a.first[d] = (uint32_t)(r % a.n[d]);
+                r /= a.n[d];
+            }
+            a.nrows = (uint32_t)n;
+            if (!emit(a, strided_launch_groups(p, n))) return;
+        }
+        int d = ki;
+        while (d < b.k && ++at[d] == b.n[d]) at[d++] = 0;
+        if (d >= b.k) return;
+    }
+}
+
+// the argument checks MPIR_Hip_reduce_subarray makes before it looks at a
+// pointer: the pair's kernels, then the box
+int subarray_args(const int *in_sizes, const int *in_starts, const int *io_sizes, const int *io_starts, int ndims,
+                  const int *subsizes, int c_order, int op, int elem, SubarrayBox &b) {
+    if (!pair_in_range(op, elem) || !g_subarray[op][elem].launch || !g_strided[op][elem].launch ||
+        !g_batch[op][elem].groups)
+        return MPIR_HIP_ENOKERNEL;
+    return subarray_box(in_sizes, in_starts, io_sizes, io_starts, ndims, subsizes, c_order, g_elem_size[elem], b);
 }
 
 // the argument checks MPIR_Hip_reduce_indexed makes before it looks at a
@@ -896,6 +1050,88 @@ int MPIR_Hip_reduce_strided(const void *inbuf, uint64_t in_stride, void *inoutbu
     hipError_t e = hipSuccess;
     strided_launches(p, inbuf, in_stride, inoutbuf, io_stride, nblocks, blocklen, f.each(g_strided[op][elem].launch, e));
     return f.close(e, "strided launch");
+}
+
+int MPIR_Hip_subarray_plan_info(const void *inbuf, const int *in_sizes, const int *in_starts, const void *inoutbuf,
+                                const int *io_sizes, const int *io_starts, int ndims, const int *subsizes, int c_order,
+                                int op, int elem, uint64_t out[MPIR_HIP_SUBARRAY_PLAN_WORDS]) {
+    SubarrayBox b;
+    int rc = subarray_args(in_sizes, in_starts, io_sizes, io_starts, ndims, subsizes, c_order, op, elem, b);
+    if (rc != MPIR_HIP_OK) return rc;
+    for (int k = 0; k < MPIR_HIP_SUBARRAY_PLAN_WORDS; ++k) out[k] = 0;
+    const char *in = static_cast<const char *>(inbuf) + b.in_off, *io = static_cast<const char *>(inoutbuf) + b.io_off;
+    out[5] = mpir_hip::g_strided_wide.load(std::memory_order_relaxed);
+    out[7] = (uint64_t)b.k;
+    out[8] = b.blocklen;
+    out[9] = b.in_off;
+    out[10] = b.io_off;
+    for (int d = 0; d < b.k; ++d) {
+        out[16 + d] = b.n[d];
+        out[24 + d] = b.in_stride[d];
+        out[32 + d] = b.io_stride[d];
+    }
+    if (b.k == 0) {
+        out[0] = MPIR_HIP_SUBARRAY_SINGLE;
+        out[1] = 1;
+        out[6] = 1;
+        return single_plan(in, io, b.blocklen, op, elem, &out[2]);
+    }
+    if (b.k == 1) {
+        // the strided call's own report of the five numbers it is handed
+        uint64_t s[8];
+        rc = MPIR_Hip_strided_plan_info(in, b.in_stride[0], io, b.io_stride[0], b.n[0], b.blocklen, op, elem, s);
+        if (rc != MPIR_HIP_OK) return rc;
+        out[0] = MPIR_HIP_SUBARRAY_STRIDED;
+        out[1] = s[1];
+        out[2] = s[2];
+        out[3] = s[3];
+        out[5] = s[6];
+        out[6] = s[7];
+        out[11] = s[0];
+        out[12] = s[4];
+        out[13] = s[5];
+        return MPIR_HIP_OK;
+    }
+    StridedPlan p;
+    uint64_t peel = 1;
+    subarray_plan(b, in, io, elem, p, &peel);
+    out[0] = (uint64_t)p.form;
+    out[1] = peel * p.launches;
+    out[2] = peel * p.groups;
+    out[3] = p.per;
+    out[4] = p.upr;
+    out[6] = p.rows_per_launch;
+    return MPIR_HIP_OK;
+}
+
+int MPIR_Hip_reduce_subarray(const void *inbuf, const int *in_sizes, const int *in_starts, void *inoutbuf,
+                             const int *io_sizes, const int *io_starts, int ndims, const int *subsizes, int c_order,
+                             int op, int elem, void *hip_stream, int sync) {
+    SubarrayBox b;
+    int rc = subarray_args(in_sizes, in_starts, io_sizes, io_starts, ndims, subsizes, c_order, op, elem, b);
+    if (rc != MPIR_HIP_OK) return rc;
+    ctx().err[0] = 0;
+    // the first and the last byte of each operand's box, before anything is
+    // launched: a call that fails has written nothing
+    const char *in = static_cast<const char *>(inbuf) + b.in_off;
+    char *io = static_cast<char *>(inoutbuf) + b.io_off;
+    Residency r;
+    if (!r.operand(0, in, b.in_span) || !r.operand(1, io, b.io_span)) return MPIR_HIP_EBUFFER;
+    // a box that is one run is the single call, one that is rows at one stride
+    // the strided call: their planners, kernels and plans, not restated here
+    if (b.k == 0) return MPIR_Hip_reduce(in, io, b.blocklen, op, elem, hip_stream, sync);
+    if (b.k == 1)
+        return MPIR_Hip_reduce_strided(in, b.in_stride[0], io, b.io_stride[0], b.n[0], b.blocklen, op, elem, hip_stream,
+                                       sync);
+    StridedPlan p;
+    uint64_t peel = 1;
+    subarray_plan(b, in, io, elem, p, &peel);
+    if ((rc = plan_fits(p, "a subarray row needs more workgroups than one launch holds")) != MPIR_HIP_OK) return rc;
+    Frame f(r.dev, hip_stream, sync);
+    if ((rc = f.open()) != MPIR_HIP_OK) return rc;
+    hipError_t e = hipSuccess;
+    subarray_launches(b, p, in, io, f.each(g_subarray[op][elem].launch, e));
+    return f.close(e, "subarray launch");
 }
 
 int MPIR_Hip_indexed_plan_info(const void *inbuf, const int64_t *in_displs, const void *inoutbuf,

@@ -223,9 +223,11 @@ static const char *class_string(int cls)
         return "Invalid root";
     case MPI_ERR_OP:
         return "Invalid MPI_Op";
+    case MPI_ERR_DIMS:
+        return "Invalid dimension argument";
     case MPI_ERR_ARG:
         return "Invalid argument";
-    case 14:   /* MPI_ERR_TRUNCATE */
+    case 14:  /* MPI_ERR_TRUNCATE */
         return "Message truncated";
     case MPI_ERR_OTHER:
         return "Other MPI error";

@@ -567,6 +567,96 @@ int MPIX_Reduce_local_strided(const void *inbuf, MPI_Aint in_stride, void *inout
                                    hip_stream));
 }
 
+/* ---- MPIX_Reduce_local_subarray: sub-boxes of N-d arrays (see the header) */
+#pragma weak MPIR_Hip_reduce_subarray
+/* one dimension of one operand as type_create_subarray.c:105-133 checks it */
+static int subarray_dim_ok(const char *side, int d, int size, int subsize, int start)
+{
+    if (size < 1 || subsize < 1 || start < 0) {
+        MPIR_Err_set_detail("%s dimension %d: %s %d", side, d,
+                            size < 1 ? "size" : subsize < 1 ? "subsize" : "negative start",
+                            size < 1 ? size : subsize < 1 ? subsize : start);
+        return 0;
+    }
+    if (subsize > size || start > size - subsize) {
+        MPIR_Err_set_detail("%s dimension %d: %s %d is above %d", side, d, subsize > size ? "subsize" : "start",
+                            subsize > size ? subsize : start, subsize > size ? size : size - subsize);
+        return 0;
+    }
+    return 1;
+}
+
+static int reduce_local_subarray(const void *inbuf, const int in_sizes[], const int in_starts[], void *inoutbuf,
+                                 const int inout_sizes[], const int inout_starts[], int ndims, const int subsizes[],
+                                 int order, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    static const char *fc = "MPIX_Reduce_local_subarray";
+    int mpi_errno, opidx, elem, rc, d, side;
+    /* the op and the type first, as the strided call validates them */
+    if ((mpi_errno = validate(NULL, NULL, 0, datatype, op)) != MPI_SUCCESS ||
+        (mpi_errno = builtin_op_elem(datatype, op, &opidx, &elem)) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
+    if (ndims < 1 || ndims > MPIX_REDUCE_LOCAL_SUBARRAY_MAXDIMS) {
+        MPIR_Err_set_detail("ndims %d is not in 1..%d", ndims, MPIX_REDUCE_LOCAL_SUBARRAY_MAXDIMS);
+        return err_return(fc, MPI_ERR_DIMS);
+    }
+    if (!subsizes || (in_sizes && !in_starts) || (inout_sizes && !inout_starts)) {
+        MPIR_Err_set_detail("Null pointer in parameter %s", !subsizes ? "subsizes" : in_sizes &&
+                            !in_starts ? "in_starts" : "inout_starts");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    if (order != MPI_ORDER_C && order != MPI_ORDER_FORTRAN) {
+        MPIR_Err_set_detail("Invalid argument order");
+        return err_return(fc, MPI_ERR_ARG);
+    }
+    for (d = 0; d < ndims; d++)
+        if (!subarray_dim_ok("inbuf", d, in_sizes ? in_sizes[d] : subsizes[d], subsizes[d], in_sizes ? in_starts[d] : 0) ||
+            !subarray_dim_ok("inoutbuf", d, inout_sizes ? inout_sizes[d] : subsizes[d], subsizes[d],
+                             inout_sizes ? inout_starts[d] : 0))
+            return err_return(fc, MPI_ERR_ARG);
+    /* the reference's **subarrayoflow: the whole array's bytes in an MPI_Aint */
+    for (side = 0; side < 2; side++) {
+        const int *sizes = side ? inout_sizes : in_sizes;
+        MPI_Aint bytes = (MPI_Aint) MPIR_Hip_elem_size(elem);
+        for (d = 0; d < ndims; d++)
+            if (__builtin_mul_overflow(bytes, (MPI_Aint) (sizes ? sizes[d] : subsizes[d]), &bytes)) {
+                MPIR_Err_set_detail("the size of %s's array does not fit an MPI_Aint", side ? "inoutbuf" : "inbuf");
+                return err_return(fc, MPI_ERR_ARG);
+            }
+    }
+    if (inbuf == MPI_IN_PLACE || inoutbuf == MPI_IN_PLACE) {
+        MPIR_Err_set_detail("buffer '%s' cannot be MPI_IN_PLACE", inbuf == MPI_IN_PLACE ? "inbuf" : "inoutbuf");
+        return err_return(fc, MPI_ERR_BUFFER);
+    }
+    if (inbuf == inoutbuf && alias_check_enabled()) {
+        /* one array on both sides is the periodic wrap: legal where the two
+         * boxes are disjoint, which the starts of one dimension show */
+        int apart = 0;
+        if (in_sizes && inout_sizes && !memcmp(in_sizes, inout_sizes, (size_t) ndims * sizeof(int)))
+            for (d = 0; d < ndims; d++) {
+                const long gap = (long) in_starts[d] - (long) inout_starts[d];
+                apart |= (gap < 0 ? -gap : gap) >= (long) subsizes[d];
+            }
+        if (!apart) {
+            MPIR_Err_set_detail("Buffers must not be aliased (one array on both sides needs equal sizes and disjoint boxes)");
+            return err_return(fc, MPI_ERR_BUFFER);
+        }
+    }
+    if ((mpi_errno = shim_has(MPIR_Hip_reduce_subarray != NULL, "MPIR_Hip_reduce_subarray")) != MPI_SUCCESS)
+        return err_return(fc, mpi_errno);
+    rc = MPIR_Hip_reduce_subarray(inbuf, in_sizes, in_starts, inoutbuf, inout_sizes, inout_starts, ndims, subsizes,
+                                  order == MPI_ORDER_C, opidx, elem, hip_stream, hip_stream == NULL);
+    return shim_result(fc, rc, EBUF_BUFFERS, "%s: the arrays' sizes, subsizes or starts are out of range");
+}
+
+int MPIX_Reduce_local_subarray(const void *inbuf, const int in_sizes[], const int in_starts[], void *inoutbuf,
+                               const int inout_sizes[], const int inout_starts[], int ndims, const int subsizes[],
+                               int order, MPI_Datatype datatype, MPI_Op op, void *hip_stream)
+{
+    CS_RETURN(reduce_local_subarray(inbuf, in_sizes, in_starts, inoutbuf, inout_sizes, inout_starts, ndims, subsizes,
+                                    order, datatype, op, hip_stream));
+}
+
 /* ---- MPIX_Reduce_local_fetch: old value out, combine in (see the header) */
 #pragma weak MPIR_Hip_reduce_fetch
 static int ranges_overlap(const void *a, const void *b, uint64_t bytes)

@@ -114,6 +114,7 @@ EXPORTED_SYMBOLS = [
     "MPIX_Reduce_local_batch", "MPIR_Hip_reduce_batch", "MPIR_Hip_batch_plan_info",
     "MPIX_Reduce_local_strided", "MPIR_Hip_reduce_strided", "MPIR_Hip_strided_plan_info",
     "MPIR_Hip_set_strided_wide_bytes", "MPIR_Hip_strided_test_max_groups",
+    "MPIX_Reduce_local_subarray", "MPIR_Hip_reduce_subarray", "MPIR_Hip_subarray_plan_info",
     "MPIX_Reduce_local_fetch", "MPIR_Hip_reduce_fetch", "MPIR_Hip_fetch_plan_info",
     "MPIX_Reduce_local_indexed", "MPIR_Hip_reduce_indexed", "MPIR_Hip_indexed_plan_info",
     "MPIX_Reduce_local_indexed_ordered", "MPIR_Hip_reduce_indexed_ordered", "MPIR_Hip_indexed_ordered_plan_info",
@@ -205,6 +206,13 @@ def load(path: str | None = None) -> ctypes.CDLL:
     for name in ("MPIR_Hip_set_strided_wide_bytes", "MPIR_Hip_strided_test_max_groups"):
         getattr(lib, name).argtypes = [u64]
         getattr(lib, name).restype = u64
+    ip = ctypes.POINTER(i32)
+    lib.MPIX_Reduce_local_subarray.argtypes = [vp, ip, ip, vp, ip, ip, i32, ip, i32, i32, i32, vp]
+    lib.MPIX_Reduce_local_subarray.restype = i32
+    lib.MPIR_Hip_reduce_subarray.argtypes = [vp, ip, ip, vp, ip, ip, i32, ip, i32, i32, i32, vp, i32]
+    lib.MPIR_Hip_reduce_subarray.restype = i32
+    lib.MPIR_Hip_subarray_plan_info.argtypes = [vp, ip, ip, vp, ip, ip, i32, ip, i32, i32, i32, ctypes.POINTER(u64)]
+    lib.MPIR_Hip_subarray_plan_info.restype = i32
     lib.MPIX_Reduce_local_fetch.argtypes = [vp, vp, vp, i32, i32, i32, vp]
     lib.MPIX_Reduce_local_fetch.restype = i32
     lib.MPIR_Hip_reduce_fetch.argtypes = [vp, vp, vp, u64, i32, i32, vp, i32]
@@ -558,6 +566,61 @@ def strided_plan_info(inbuf: int, in_stride: int, inoutbuf: int, inout_stride: i
         raise LookupError(f"MPIR_Hip_strided_plan_info: {rc}")
     return dict(zip(("form", "launches", "groups", "per", "tile_rows", "elem_rows", "threshold", "rows_per_launch"),
                     (int(v) for v in out)))
+
+
+# ---- subarray reductions (MPIX_Reduce_local_subarray)
+MPI_ERR_DIMS = 11
+MPI_ORDER_C, MPI_ORDER_FORTRAN = 56, 57
+SUBARRAY_MAXDIMS = 8
+SUBARRAY_SINGLE, SUBARRAY_WIDE, SUBARRAY_NARROW_VEC, SUBARRAY_NARROW_ELEMS, SUBARRAY_STRIDED = range(1, 6)
+SUBARRAY_NAMES = ["", "single", "wide", "narrow_vec", "narrow_elems", "strided"]
+
+
+def _ints(seq):
+    """An int array for the C ABI, or None (a packed operand's sizes and starts)."""
+    return None if seq is None else (ctypes.c_int * max(len(seq), 1))(*seq)
+
+
+def reduce_local_subarray(inbuf: int, in_sizes, in_starts, inoutbuf: int, inout_sizes, inout_starts, subsizes,
+                          order: int, datatype: int, op: int, stream: int = 0, ndims: int | None = None) -> int:
+    """MPIX_Reduce_local_subarray: the sub-box subsizes of the array in_sizes at
+    in_starts combined into the one of inout_sizes at inout_starts (raw device
+    addresses of the arrays' origins; sequences of ints; sizes None: that side is
+    packed).  ndims defaults to len(subsizes).  stream 0: synchronous on the
+    library stream; otherwise enqueued on that HIP stream, no wait."""
+    n = len(subsizes) if ndims is None else ndims
+    return load().MPIX_Reduce_local_subarray(ctypes.c_void_p(inbuf or None), _ints(in_sizes), _ints(in_starts),
+                                             ctypes.c_void_p(inoutbuf or None), _ints(inout_sizes), _ints(inout_starts),
+                                             n, _ints(subsizes), order, datatype, op, ctypes.c_void_p(stream or None))
+
+
+def subarray_plan_info(inbuf: int, in_sizes, in_starts, inoutbuf: int, inout_sizes, inout_starts, subsizes, order: int,
+                       datatype: int, op: int) -> dict:
+    """MPIR_Hip_subarray_plan_info: the normal form and the launches of a subarray
+    reduction of device operands at these addresses (never dereferenced; no GPU
+    needed): form (SUBARRAY_*), launches, groups (over all launches), per (WIDE:
+    G; NARROW: units per workgroup), units_per_row (NARROW), threshold,
+    rows_per_launch, k, blocklen, in_offset / io_offset (bytes from the arrays'
+    origins to the boxes), n / in_stride / io_stride (the k outer dimensions,
+    fastest first, strides in bytes) and, for SUBARRAY_STRIDED, strided_form,
+    tile_rows and elem_rows as strided_plan_info reports them.  Raises LookupError
+    where the pair has no kernel, ValueError for arguments the call refuses."""
+    out = (ctypes.c_uint64 * 40)()
+    rc = load().MPIR_Hip_subarray_plan_info(ctypes.c_void_p(inbuf or None), _ints(in_sizes), _ints(in_starts),
+                                            ctypes.c_void_p(inoutbuf or None), _ints(inout_sizes), _ints(inout_starts),
+                                            len(subsizes), _ints(subsizes), int(order == MPI_ORDER_C), op & 0xFF,
+                                            _ELEM_BY_HANDLE[datatype], out)
+    if rc == MPIR_HIP_EARG:
+        raise ValueError("MPIR_Hip_subarray_plan_info: arguments refused")
+    if rc:
+        raise LookupError(f"MPIR_Hip_subarray_plan_info: {rc}")
+    d = dict(zip(("form", "launches", "groups", "per", "units_per_row", "threshold", "rows_per_launch", "k", "blocklen",
+                  "in_offset", "io_offset", "strided_form", "tile_rows", "elem_rows"), (int(v) for v in out)))
+    k = d["k"]
+    d["n"] = [int(out[16 + j]) for j in range(k)]
+    d["in_stride"] = [int(out[24 + j]) for j in range(k)]
+    d["io_stride"] = [int(out[32 + j]) for j in range(k)]
+    return d
 
 
 # ---- fetching reductions (MPIX_Reduce_local_fetch)
